@@ -8,6 +8,12 @@ per-GPU batch runs data-parallel (weak scaling, one RCCL all-reduce per step).
 One step = convnet_layers -> rnn_layers -> ctc_loss_layer forward, backward,
 gradient all-reduce (N > 1) and the Adam kernel, on synthetic uint8 crops and
 labels already resident in HBM. Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and
+prints the line (with the roofline figures its probes take inside the timed
+steps). --full adds the legs that take runs of their own, after the timing: the
+CER checks, the CPU baseline, the C1 latency, and in --mode graph the read-back
+replays that average the roofline probes over --steps steps.
 """
 import argparse
 import hashlib
@@ -49,6 +55,22 @@ def synthetic_batch(rng, B, W, T, device):
         lab[b, :L] = s
         ln[b] = L
     return img, widths, (torch.from_numpy(lab).to(device), torch.from_numpy(ln).to(device))
+
+
+DUMP_MAX_VALUES = 4 * 1024 * 1024     # per array: 16 MB of float32 (a run writes at most 4 large arrays)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` {name: tensor} as path/<name>.npy in float32. An
+    array of more than DUMP_MAX_VALUES values is stored as a fixed sample of that
+    many (seed 0, ascending flat indices: the same positions in every run)."""
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_VALUES, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def work_conv_fwd(args):
@@ -317,7 +339,7 @@ def cer_vs_ref_trained(device):
         truth[0] += float(d.sum())
         truth[1] += int(ln.sum().item())
         rows += len(labels)
-    res = {"data": f"tests/golden/mjsynth_test_words000.npz (data/test shard, {rows} crops, server buckets, uint8); "
+    res = {"data": f"tests/golden/mjsynth_test_words000.part*.npz (data/test shard, {rows} crops, server buckets, uint8); "
                    "weights: fp32 training on data/val (tests/trained_model.py REGIME, "
                    f"{TM.REGIME['steps']} steps, {train_s:.0f} s)",
            "reference": "the fp32 HIP path's strings (= the float64 graph's on all 932 served rows but one beam "
@@ -364,11 +386,13 @@ def run_c2(args, world, rank, device):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, dense = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "decoded": dense})
     return {"metric": "line-crops/sec (fwd + CTC loss + greedy decode) at 32x256 bs=64",
             "value": round(world * B * args.steps / elapsed, 2), "unit": "line-crops/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
@@ -453,22 +477,28 @@ def run_c5(args, world, rank, device, n_crops=2048, beam=16):
         if dec_stream is not None:
             main.wait_stream(dec_stream)
         return out
-    for _ in range(max(1, args.warmup // 2)):
+    for _ in range(args.warmup):
         run()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    reps = max(1, args.steps // 4)
+    reps = args.steps             # one timed step = one pass over this rank's buckets
     for _ in range(reps):
-        run()
+        out = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = (time.perf_counter() - t0) / reps
+    if args.dump_outputs and rank == 0:
+        arrays = {}
+        for (img, _w), (paths, _len, logp) in zip(batches, out):
+            arrays[f"decoded_w{img.shape[2]}"] = paths[0]
+            arrays[f"log_prob_w{img.shape[2]}"] = logp
+        dump_outputs(args.dump_outputs, arrays)
     return {"metric": "line-crops/sec (bucketed 32x{64..512}, INFER + beam-16 decode)",
             "value": round(n_crops / elapsed, 2), "unit": "line-crops/sec", "n_gpus": world, "steps": reps,
-            "warmup": max(1, args.warmup // 2), "ms_per_step": round(1e3 * elapsed, 3), "higher_is_better": True,
+            "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed, 3), "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32",
             "data": f"synthetic: {n_crops} uint8 crops, true widths U{{65..512}}, server-style 32-px buckets",
             "config": {"workload": "C5: bucketed INFER + CTC beam search (beam 16), LSTM 512/512",
@@ -670,10 +700,20 @@ def main():
                     help="C3 with N > 1: BatchNorm statistics over all ranks' batches (Trainer(sync_bn=True))")
     ap.add_argument("--main-stream", choices=("default", "own"), default="default",
                     help="run the train step on torch's default (NULL) stream or on a non-blocking stream of its own")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cer", action="store_true", help="skip the CER-vs-oracle decode check (outside the timing)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: the CER checks, "
+                         "the CPU baseline and the C1 latency (C3, each with its --no-* switch), and in --mode "
+                         "graph the read-back replays that average the roofline probes over --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; C3: loss, the updated parameters, BatchNorm moving statistics and Adam first "
+                         "moments, each at most 16 MB -- a fixed seeded sample of a larger array; C2: loss and "
+                         "decodes; C5: each bucket's best path and log-probability). Rank 0's outputs.")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and C1 latency legs")
+    ap.add_argument("--no-cer", action="store_true",
+                    help="--full: skip the CER-vs-oracle decode check (outside the timing)")
     ap.add_argument("--no-trained-cer", action="store_true",
-                    help="skip the trained-weight CER leg (~25 s: trains the model on data/val first)")
+                    help="--full: skip the trained-weight CER leg (~25 s: trains the model on data/val first)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "pmc_conv.json"),
                     help="PMC summary (tools/pmc_traffic.py) for roofline.traffic of the conv roofline kernel")
     ap.add_argument("--selftest", action="store_true",
@@ -809,22 +849,29 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     _lib.PROBES.clear()
+    # the timers in the graph hold the last timed step; --full: K - 1 more replays, each
+    # read back after a sync, complete the average over K steps
+    graph_reads = args.steps if args.full else 1
     if args.mode == "graph":
-        probed = args.steps
+        probed = graph_reads
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned (the loss) and left behind for its caller: the
+        # updated variables, the BatchNorm moving statistics and Adam's first moments (the
+        # step's gradient enters them; the gradient buffer itself is cleared by the update)
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": store.flat,
+                                         "bn_stats": store.flat_stats, "adam_m": trainer.m})
 
     def read(records):
         return [a.elapsed_ms(b) for a, b, _ in records]
 
     mss = {k: read(r) for k, r in probes.items()}
     if args.mode == "graph":
-        # the timers in the graph hold the last timed step; K more replays, each
-        # read back after a sync, complete the average over K steps
         rows = {n: read(r) for n, r in table.items() if r}
-        for _ in range(args.steps - 1):
+        for _ in range(graph_reads - 1):
             run_step()
             torch.cuda.synchronize()
             for k, r in probes.items():
@@ -832,7 +879,7 @@ def main():
             for n, r in table.items():
                 if r:
                     rows[n] += read(r)
-        works = {k: sum(w for _, _, w in r) * args.steps for k, r in probes.items()}
+        works = {k: sum(w for _, _, w in r) * graph_reads for k, r in probes.items()}
     else:
         rows = {n: read(r) for n, r in table.items() if r}
         works = {k: sum(w for _, _, w in r) for k, r in probes.items()}
@@ -885,7 +932,7 @@ def main():
                      "algorithmic_flop_per_launch": work / max(len(ms), 1),
                      "timing": "HIP events bracketing each launch on its stream" + (
                          " (external event nodes inside the step graph; last timed step + "
-                         f"{args.steps - 1} read-back replays)" if args.mode == "graph" else
+                         f"{graph_reads - 1} read-back replays)" if args.mode == "graph" else
                          f" in {probed} of the {args.steps} timed steps (every {every}th)")},
         "loss": round(float(loss.item()), 4),
     }
@@ -915,11 +962,11 @@ def main():
         else:
             result["roofline"]["traffic_note"] = (f"{src} was taken of another libocrk.so build "
                                                   f"({str(pmc.get('libocrk_sha256'))[:12]} vs {lib_sha[:12]}): not reported")
-    if rank == 0 and not args.no_cer and args.cell == "lstm":      # the golden decodes are of the LSTM model
+    if rank == 0 and args.full and not args.no_cer and args.cell == "lstm":   # the golden decodes are of the LSTM model
         result["cer_vs_ref"] = cer_vs_ref(device)
         if world == 1 and not args.no_trained_cer:
             result["cer_vs_ref_trained"] = cer_vs_ref_trained(device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.cpu_sample, steps=args.cpu_steps, cell=args.cell)
         if args.cell == "lstm":
             result["c1_latency"] = c1_latency(device)

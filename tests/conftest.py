@@ -7,7 +7,24 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE_DATA = "/root/reference/data"
+# the reference's own data shards (data/{test,val}/words-000.tfrecord), each stored as two
+# files of whole records, in record order (words-000-0, words-000-1), each under 1 MB
+REFERENCE_DATA = os.path.join(ROOT, "tests", "golden", "tfrecord")
+
+
+def shard_files(split):
+    """The files of data/<split>/words-000, in record order."""
+    import glob
+    files = sorted(glob.glob(os.path.join(REFERENCE_DATA, split, "words-000-*.tfrecord")))
+    assert len(files) == 2, files
+    return files
+
+
+def shard_records(split, verify_crc=False):
+    """Every record of data/<split>/words-000, in the shard's order."""
+    from cnn_lstm_ctc_ocr_amd.tfrecord import read_word_records
+    for path in shard_files(split):
+        yield from read_word_records(path, verify_crc=verify_crc)
 
 
 def pytest_configure(config):

@@ -5,7 +5,7 @@ The reference trains (src/weinman/train.py:168-201) and serves a trained model
 are nearly degenerate, so decode parity there is checked only on easy rows.
 Here the LSTM 512/512 model is trained from seed 0 on the reference's own data
 -- every crop of data/val/words-000.tfrecord (tests/golden/
-mjsynth_val_words000.npz, tools/make_val_fixture.py) through the training input
+mjsynth_val_words000.part*.npz, tools/make_val_fixture.py) through the training input
 semantics (first-row pad, 0.0 dynamic padding, mjsynth.py:185-194) in
 width-sorted batches of 32, a seeded shuffle per epoch -- under
 tests/trained_model.py's REGIME (Adam with the reference's exponential decay,

@@ -2,15 +2,12 @@
 import os
 
 import numpy as np
-import pytest
 
 from cnn_lstm_ctc_ocr_amd import input_pipeline as P
 from cnn_lstm_ctc_ocr_amd.mjsynth import encode
-from cnn_lstm_ctc_ocr_amd.tfrecord import read_word_records
 
-from conftest import REFERENCE_DATA
+from conftest import REFERENCE_DATA, shard_records
 
-needs_data = pytest.mark.skipif(not os.path.isdir(REFERENCE_DATA), reason="reference data shards absent")
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "mjsynth_test_bucket.npz")
 
 
@@ -43,19 +40,17 @@ def test_make_batch_pads_height_and_width_with_zero():
     assert idx.tolist() == [[0, 0], [0, 1], [1, 0]] and vals.tolist() == [1, 2, 3] and shape.tolist() == [2, 2]
 
 
-@needs_data
 def test_records_labels_are_the_charset_encoding_of_the_text():
     n = 0
-    for r in read_word_records(os.path.join(REFERENCE_DATA, "test", "words-000.tfrecord"), verify_crc=True):
+    for r in shard_records("test", verify_crc=True):
         assert r["labels"] == encode(r["text"]) and r["length"] == len(r["text"])
         n += 1
     assert n == 892
 
 
-@needs_data
 def test_bucketed_pipeline_one_epoch_covers_every_kept_record():
     base = os.path.join(REFERENCE_DATA, "test")
-    kept = [r for r in read_word_records(os.path.join(base, "words-000.tfrecord"))
+    kept = [r for r in shard_records("test")
             if r["width"] <= 200 and r["length"] <= 12]
     seen = []
     for image, width, label, length, text, fn in P.bucketed_input_pipeline(
@@ -68,12 +63,11 @@ def test_bucketed_pipeline_one_epoch_covers_every_kept_record():
     assert sorted(seen) == sorted(r["filename"] for r in kept)
 
 
-@needs_data
 def test_golden_fixture_is_the_pipeline_batch():
     """tests/golden/mjsynth_test_bucket.npz holds exactly what the pipeline makes."""
     with np.load(GOLDEN, allow_pickle=False) as z:
         x, widths, texts = z["x_f32"], z["widths"], z["texts"]
-    recs = [r for r in read_word_records(os.path.join(REFERENCE_DATA, "test", "words-000.tfrecord"))
+    recs = [r for r in shard_records("test")
             if 96 < r["width"] <= 128][:len(widths)]
     items = [{"image": P.preprocess_image(P.decode_jpeg_gray(r["image"])), "width": r["width"],
               "labels": r["labels"], "length": r["length"], "text": r["text"], "filename": r["filename"]}

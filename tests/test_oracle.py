@@ -1,7 +1,7 @@
 """Pin the CPU oracle (oracle/) before trusting it as the parity checker.
 
-Sources of truth, in order: the reference's own fixture data (TFRecord shards
-under /root/reference/data, when present), known-answer tests (brute-force CTC
+Sources of truth, in order: the reference's own fixture data (its TFRecord
+shards, stored under tests/golden/tfrecord), known-answer tests (brute-force CTC
 path sums, hand-made greedy cases, finite differences), and independent
 PyTorch-CPU implementations where TF1 semantics coincide.
 """
@@ -15,7 +15,7 @@ import torch.nn.functional as F
 from oracle import ref_graph as G
 from oracle import ref_model as M
 
-from conftest import REFERENCE_DATA
+from conftest import shard_records
 
 torch.set_num_threads(min(8, os.cpu_count() or 1))
 
@@ -36,14 +36,11 @@ def test_charset_constants():
     assert G.get_string([12, 14, 13, 8, 10, 4, 17]) == "MONIKER"
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_DATA), reason="reference data not mounted")
 def test_reference_tfrecords_pin_label_encoding():
     """Every record of the reference's own shards: labels == encode(text)."""
-    from cnn_lstm_ctc_ocr_amd.tfrecord import read_word_records
     n = 0
     for split in ("test", "val"):
-        for r in read_word_records(os.path.join(REFERENCE_DATA, split, "words-000.tfrecord"),
-                                   verify_crc=True):
+        for r in shard_records(split, verify_crc=True):
             assert r["labels"] == G.encode_text(r["text"])
             assert r["length"] == len(r["text"])
             n += 1

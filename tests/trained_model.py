@@ -29,16 +29,35 @@ import numpy as np
 import torch
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# nominal names: each shard is stored as <name>.part0.npz, .part1.npz, ... (load_shard)
 TRAIN_SHARD = os.path.join(GOLDEN_DIR, "mjsynth_val_words000.npz")
 HELD_OUT_SHARD = os.path.join(GOLDEN_DIR, "mjsynth_test_words000.npz")
 REGIME = dict(lr=1e-3, decay_rate=0.5, decay_steps=1000, steps=4000, batch=32, seed=0, order_seed=7)
+
+
+def load_shard(path):
+    """The shard fixture `<name>.npz`, stored as `<name>.part0.npz`, `<name>.part1.npz`,
+    ... (consecutive crop ranges in the layout of tools/make_val_fixture.py, each
+    file under 1 MB), joined back into the whole shard's arrays."""
+    stem = path[:-len(".npz")]
+    parts = []
+    while os.path.exists(f"{stem}.part{len(parts)}.npz"):
+        with np.load(f"{stem}.part{len(parts)}.npz", allow_pickle=False) as z:
+            parts.append({k: z[k] for k in z.files})
+    if not parts:
+        raise FileNotFoundError(f"{stem}.part0.npz")
+    g = {k: np.concatenate([p[k] for p in parts]) for k in ("widths", "heights", "labels", "label_len", "texts")}
+    g["pixels"] = np.concatenate([p["pixels"] for p in parts], axis=1)
+    starts = np.cumsum([0] + [p["pixels"].shape[1] for p in parts[:-1]])
+    g["offsets"] = np.concatenate([p["offsets"] + s for p, s in zip(parts, starts)])
+    return g
 
 
 def shard_items(path):
     """Every crop of a shard fixture, in width order, through the training input
     semantics (first-row pad, mjsynth.py:185-194)."""
     from cnn_lstm_ctc_ocr_amd import input_pipeline as P
-    g = np.load(path)
+    g = load_shard(path)
     order = np.argsort(g["widths"], kind="stable")
     items = []
     for i in order:

@@ -6,7 +6,7 @@ set -o pipefail
 tag=${1:?tag}
 out=gpurun_out/ev_$tag
 mkdir -p "$out"
-timeout -k 10 300 python3 -u bench.py > "$out/bench.log" 2>&1 || exit $?
+timeout -k 10 300 python3 -u bench.py --full > "$out/bench.log" 2>&1 || exit $?
 grep '^{' "$out/bench.log" | tail -1 > "$out/bench.json"
 timeout -k 10 200 python3 -u bench.py --cell gru --no-cpu-baseline > "$out/bench_gru.log" 2>&1 || exit $?
 grep '^{' "$out/bench_gru.log" | tail -1 > "$out/bench_gru.json"

@@ -3,7 +3,7 @@ reference's data/test shard (one width bucket, (96, 128]) through the
 reference input-pipeline semantics, plus the float64 oracle's outputs with the
 reference initialisers (seed 0, LSTM 512/512, model_bu.py).
 
-    python tools/make_golden.py        (needs /root/reference/data; run here, not on the GPU box)
+    python tools/make_golden.py        (reads the shard stored under tests/golden/tfrecord/test/)
 
 Stored: the preprocessed float32 batch exactly as mjsynth.py would feed it
 (first-row pad, 0.0 dynamic padding), the raw uint8 crops right-padded with 0
@@ -29,7 +29,8 @@ N, LO, HI = 8, 96, 128
 
 def main():
     recs = []
-    for r in read_word_records("/root/reference/data/test/words-000.tfrecord"):
+    shard = os.path.join(ROOT, "tests", "golden", "tfrecord", "test", "words-000-0.tfrecord")
+    for r in read_word_records(shard):       # the first 8 crops of the bucket are in the shard's first file
         if LO < r["width"] <= HI:
             recs.append(r)
         if len(recs) == N:

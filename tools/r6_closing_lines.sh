@@ -3,7 +3,7 @@
 # and the other configurations, into gpurun_out/lines/.
 set -o pipefail
 out=gpurun_out/lines; mkdir -p $out
-timeout -k 10 400 python3 bench.py > $out/bench_final.json 2> $out/bench_final.err || { tail -5 $out/bench_final.err; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $out/bench_final.json 2> $out/bench_final.err || { tail -5 $out/bench_final.err; exit 1; }
 echo "default $(grep -o '"ms_per_step": [0-9.]*' $out/bench_final.json)"
 timeout -k 10 200 python3 bench.py --cell gru --steps 30 --no-cpu-baseline --no-cer --no-trained-cer > $out/bench_gru.json 2> $out/bench_gru.err || exit 1
 timeout -k 10 200 python3 bench.py --config c2 --steps 30 --no-cpu-baseline --no-cer --no-trained-cer > $out/bench_c2.json 2> $out/bench_c2.err || exit 1

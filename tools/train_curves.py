@@ -33,7 +33,7 @@ def main():
     dev = torch.device("cuda:0")
     batches = shard_batches()
     res = {"steps": args.steps, "lr": args.lr, "batches": len(batches), "batch": 32,
-           "data": "tests/golden/mjsynth_val_words000.npz (reference data/val/words-000.tfrecord, 803 crops)"}
+           "data": "tests/golden/mjsynth_val_words000.part*.npz (reference data/val/words-000.tfrecord, 803 crops)"}
     for name, dt in (("fp32", torch.float32), ("bf16", torch.bfloat16)):
         store = ParamStore(ModelConfig(cell="lstm", rnn_sizes=(512, 512), dtype=dt), device=dev, seed=0)
         tr = Trainer(store, learning_rate=args.lr)
