@@ -517,9 +517,10 @@ lstm_fwd_r16_kernel(const bf16* __restrict__ gx, const bf16* __restrict__ whT, b
         const int64_t tb = ((int64_t)t * B + b0 + er) * 2 + dir;
         unsigned lg[4];
         auto load_gx = [&]() {                           // 4 buffer loads: 2 units x 4 gates
+            // nt: read once, streamed past the L2 that holds the exchanged rows (see step 7)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                lg[k] = __builtin_amdgcn_raw_buffer_load_b32(gx_rsrc, (int)((tb * G4 + k * H + u0 + eu) * 2), 0, 0);
+                lg[k] = __builtin_amdgcn_raw_buffer_load_b32(gx_rsrc, (int)((tb * G4 + k * H + u0 + eu) * 2), 0, 2);
         };
         floatx4 acc[2];
         acc[0] = acc[1] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -621,14 +622,23 @@ lstm_fwd_r16_kernel(const bf16* __restrict__ gx, const bf16* __restrict__ whT, b
         if (tid == 0) raise_flag(gflags + member, base + (unsigned)(s + 1), local);
 
         // 7. the layer output (zeros past the length) and the tensors saved for the
-        //    backward pass (time order; they drain behind the next step)
-        *reinterpret_cast<unsigned*>(out + ((int64_t)t * B + b0 + er) * 2 * H + dir * H + u0 + eu) =
-            valid ? pack2(hn[0], hn[1]) : 0u;
-        *reinterpret_cast<unsigned*>(hprev_t + tb * H + u0 + eu) = pack2(hp[0], hp[1]);
-        *reinterpret_cast<f32x2_t*>(cprev_t + tb * H + u0 + eu) = f32x2_t{cp[0], cp[1]};
+        //    backward pass (time order). vmcnt retires in issue order, so these 7 stores
+        //    stand in front of wave 0's next poll load and of every wave's wait for the
+        //    staged rows: the hand-off waits for them (with no stores at all the step
+        //    is 0.55 us shorter). They are nontemporal: a later kernel reads them, the
+        //    hand-off never, and as streaming stores they retire sooner and leave the
+        //    XCD's L2 to the exchanged rows (2.62 -> 2.26 us per step, same bits).
+        //    Moving them does not help: deferred into the next step (behind its DMAs and
+        //    gx loads, after the rows landed, after its MFMAs, or for wave 0 alone) they
+        //    cost 0.07-0.2 us per step, nontemporal or not.
+        __builtin_nontemporal_store(valid ? pack2(hn[0], hn[1]) : 0u,
+                                    reinterpret_cast<unsigned*>(out + ((int64_t)t * B + b0 + er) * 2 * H + dir * H + u0 + eu));
+        __builtin_nontemporal_store(pack2(hp[0], hp[1]), reinterpret_cast<unsigned*>(hprev_t + tb * H + u0 + eu));
+        __builtin_nontemporal_store(f32x2_t{cp[0], cp[1]}, reinterpret_cast<f32x2_t*>(cprev_t + tb * H + u0 + eu));
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            *reinterpret_cast<unsigned*>(acts_t + tb * G4 + k * H + u0 + eu) = pack2(a4[k][0], a4[k][1]);
+            __builtin_nontemporal_store(pack2(a4[k][0], a4[k][1]),
+                                        reinterpret_cast<unsigned*>(acts_t + tb * G4 + k * H + u0 + eu));
     }
 }
 
@@ -992,13 +1002,13 @@ lstm_bwd_r16_kernel(const bf16* __restrict__ wh, bf16* __restrict__ dzx, const i
         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         unsigned la[4], ldo;
         u32x2 lcp;
-        auto load_late = [&]() {                        // 6 buffer loads
+        auto load_late = [&]() {                        // 6 buffer loads (nt: read once, as the forward's gx)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
-                la[k] = __builtin_amdgcn_raw_buffer_load_b32(act_rsrc, (int)((tb * G4 + k * H + u0 + eu) * 2), 0, 0);
-            lcp = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(cp_rsrc, (int)((tb * H + u0 + eu) * 4), 0, 0));
+                la[k] = __builtin_amdgcn_raw_buffer_load_b32(act_rsrc, (int)((tb * G4 + k * H + u0 + eu) * 2), 0, 2);
+            lcp = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(cp_rsrc, (int)((tb * H + u0 + eu) * 4), 0, 2));
             ldo = __builtin_amdgcn_raw_buffer_load_b32(
-                do_rsrc, (int)((((int64_t)t * B + b0 + er) * 2 * H + dir * H + u0 + eu) * 2), 0, 0);
+                do_rsrc, (int)((((int64_t)t * B + b0 + er) * 2 * H + dir * H + u0 + eu) * 2), 0, 2);
         };
         floatx4 acc[4];
 #pragma unroll
@@ -1105,9 +1115,12 @@ lstm_bwd_r16_kernel(const bf16* __restrict__ wh, bf16* __restrict__ dzx, const i
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tid == 0) raise_flag(gflags + member, base + (unsigned)(i + 1), local);
-        // 7. time-order copy for the weight-gradient GEMMs (drains behind the next step)
+        // 7. time-order copy for the weight-gradient GEMMs: in front of the next poll and
+        //    of the wait for the staged rows (in-order vmcnt), so nontemporal, as the
+        //    forward's step 7 (2.83 -> 2.69 us per step; deferred: 0.1-0.2 us slower)
 #pragma unroll
-        for (int k = 0; k < 4; ++k) *reinterpret_cast<unsigned*>(dG_t + tb * G4 + k * H + u0 + eu) = zv[k];
+        for (int k = 0; k < 4; ++k)
+            __builtin_nontemporal_store(zv[k], reinterpret_cast<unsigned*>(dG_t + tb * G4 + k * H + u0 + eu));
     }
     // bias partials of this 16-row slice: the 16 rows of every (gate, unit) meet in LDS
     if (bpart) {
