@@ -1,4 +1,5 @@
-// a9/a10: CTC loss + gradient w.r.t. logits, and the greedy decoder.
+// a9/a10: CTC loss + gradient w.r.t. logits, and the greedy decoder; the forced
+// alignment of a label (ocrk_ctc_align, on the loss's lattice helpers).
 //
 // ctc_loss_layer (src/weinman/model.py:224-229) calls tf.nn.ctc_loss with
 // time_major logits [T, B, C], preprocess_collapse_repeated=False,
@@ -462,7 +463,371 @@ ctc_greedy_kernel(const float* __restrict__ logits, const int* __restrict__ seq_
     for (int i = n + lane; i < T; i += 64) out[(size_t)b * T + i] = -1;
 }
 
+// ---------------------------------------------------------- forced alignment
+// The best single path of a label through the logits (Viterbi over the same
+// extended-label lattice as the loss): max-plus instead of log-sum-exp, on the
+// RAW logits -- a frame's log-sum-exp is common to all of its states, so it
+// cannot change an argmax, and without it the chosen path is one float32 add
+// and two strict compares per state, reproducible bit for bit on the host
+// (the model's ReLU'd logits tie often). One workgroup per sequence, the state
+// layout of ctc_alpha (state lane + 64 r in register r of wave 0).
+//
+// Backpointers (0, 1 or 2 states back) are one byte per state, bp[t][64 R]:
+// every lane stores its own unconditionally, so the time loop has no branch,
+// no cross-lane packing, and waits for no store. With LAT they, the jump table
+// below and the gathered emissions em[t][s] = logit(t, l'_s) live in dynamic
+// LDS; when [T][S] does not fit, the emissions are read from the logits up to
+// four steps ahead and backpointers and jumps go to the global workspace.
+//
+// The backtrace is a chain of dependent reads, so it is cut into chunks of K
+// frames: (A) one thread per (chunk, state at the chunk's last frame) walks
+// the chunk and records where it leaves it -- jump[c][s]; (B) thread 0 hops
+// from the end over the jumps, L / K steps; (C) one thread per chunk walks it
+// again from its now known state and writes the path. 2 K + L / K dependent
+// reads instead of L. Each character's first / end frame is then read off the
+// path in parallel, and all 16 waves write the outputs, the path's
+// log-probability (block sum of logit - lse along it) and the per-character
+// softmax maxima.
+// Measured at T = 125, C = 96, labels of 2..19 symbols: 29 us at B = 64 or
+// 256 (the loss on the same inputs: 25 us without, 37-39 us with its
+// gradient); 52 us with ballot-packed 2-bit backpointers and a serial backtrace.
+template <bool LAT>
+__device__ __forceinline__ float align_em(const float* __restrict__ logits, const float* em, int t, int S, int es,
+                                          int cls, int B, int C, int b) {
+    if constexpr (LAT) return em[(size_t)t * S + es];
+    else return logits[((size_t)t * B + b) * C + cls];
+}
+
+template <int R, bool LAT>
+__device__ void ctc_viterbi(const float* __restrict__ logits, const float* em, const int* lab, int S, int L, int B,
+                            int C, int b, int blank, unsigned char* bp, float* vend) {
+    const int lane = threadIdx.x & 63;
+    // emissions are read D steps ahead: one covers the LDS latency, the logits in global memory need more
+    // (two at R = 8, where four would spill)
+    constexpr int D = LAT ? 1 : R >= 8 ? 2 : 4;
+    int cls[R], es[R];
+    bool skip[R];
+    float a[R], en[D][R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        int s = lane + 64 * r;
+        cls[r] = (s < S) ? ((s & 1) ? lab[s >> 1] : blank) : blank;
+        es[r] = s < S ? s : S - 1;
+        skip[r] = (s < S) && (s & 1) && s >= 3 && lab[s >> 1] != lab[(s >> 1) - 1];
+        const float lp = align_em<LAT>(logits, em, 0, S, es[r], cls[r], B, C, b);
+        a[r] = (s < 2 && s < S) ? lp : -INFINITY;
+#pragma unroll
+        for (int d = 0; d < D; ++d)
+            en[d][r] = 1 + d < L ? align_em<LAT>(logits, em, 1 + d, S, es[r], cls[r], B, C, b) : 0.f;
+    }
+    // one time step with the emissions e of frame t
+    auto step = [&](int t, const float* e) {
+        float nxt[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float a1, a2;
+            if constexpr (R == 1) {
+                a1 = wave_shr1(a[0]);
+                a2 = wave_shr1(a1);
+            } else {
+                // (a DPP shift per register with lane 0 patched through v_readlane measured slower than
+                // these shuffles: 209 vs 162 us at T = 497, B = 16, R = 4)
+                a1 = shift_up1(a, r, lane);
+                a2 = shift_up2(a, r, lane);
+            }
+            // stay, unless one back is strictly better, unless two back is allowed and strictly better still
+            float best = a[r];
+            int p = 0;
+            if (a1 > best) { best = a1; p = 1; }
+            if (skip[r] && a2 > best) { best = a2; p = 2; }
+            nxt[r] = best + e[r];
+            bp[(size_t)t * (64 * R) + 64 * r + lane] = (unsigned char)p;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) a[r] = lane + 64 * r < S ? nxt[r] : -INFINITY;
+    };
+    // D whole steps per trip with no branch inside (the read ahead is clamped to
+    // the last frame instead of predicated), so the compiler counts its waits
+    // exactly: a step waits for its own emissions only, not for younger loads or
+    // the backpointer stores
+    int t0 = 1;
+    for (; t0 + D <= L; t0 += D) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            float e[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                e[r] = en[d][r];
+                en[d][r] = align_em<LAT>(logits, em, min(t0 + d + D, L - 1), S, es[r], cls[r], B, C, b);
+            }
+            step(t0 + d, e);
+        }
+    }
+    // fewer than D steps are left; their emissions are in en already
+#pragma unroll
+    for (int d = 0; d < D; ++d)
+        if (t0 + d < L) step(t0 + d, en[d]);
+    // the two states a path may end in
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int s = lane + 64 * r;
+        if (s == S - 1) vend[1] = a[r];
+        if (s == S - 2) vend[0] = a[r];
+    }
+}
+
+// Bytes of backpointers + jump table per sequence: bp [T][64 R] u8, then jump
+// [ceil(T / 8)][64 R] u16 (8 = the shortest chunk).
+__host__ __device__ inline size_t align_bp_bytes(int T, int R) { return (size_t)T * 64 * R; }
+__host__ __device__ inline size_t align_trace_bytes(int T, int R) {
+    return align_bp_bytes(T, R) + (size_t)((T + 7) / 8) * 64 * R * sizeof(unsigned short);
+}
+#define ALIGN_MAX_CHUNKS 128                            // L <= 128: K = 8; <= 512: 16; else 32
+
+#define ALIGN_LAT_MAX (112 * 1024)
+
+template <int R, bool LAT>
+__global__ void __launch_bounds__(CTC_THREADS)
+ctc_align_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
+                 const int* __restrict__ label_len, const int* __restrict__ seq_len, int T, int B, int C,
+                 int max_label, int* __restrict__ frame_state, int* __restrict__ span,
+                 float* __restrict__ char_conf, float* __restrict__ path_logp, int* __restrict__ status,
+                 unsigned* __restrict__ status_word, unsigned char* __restrict__ ws) {
+    extern __shared__ uint4 s_dyn[];                    // LAT: bp, jump (align_trace_bytes), then em [T][Smax]
+    __shared__ float s_lse[CTC_MAX_T];
+    __shared__ short s_path[CTC_MAX_T];
+    __shared__ int s_lab[CTC_MAX_R * 32];
+    __shared__ int s_first[CTC_MAX_R * 32], s_end[CTC_MAX_R * 32];
+    __shared__ short s_cend[ALIGN_MAX_CHUNKS];          // state at each chunk's last frame
+    __shared__ float s_vend[2];
+    __shared__ float s_part[CTC_THREADS / 64];
+    __shared__ int s_code;
+
+    const int b = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int blank = C - 1;
+    const int L = min(max(seq_len[b], 0), T);
+    const int Lab = label_len[b];
+    const int S = 2 * Lab + 1;
+    constexpr int RS = 64 * R;                          // row stride of bp and jump
+    unsigned char* bp = LAT ? reinterpret_cast<unsigned char*>(s_dyn) : ws + (size_t)b * align_trace_bytes(T, R);
+    unsigned short* jump = reinterpret_cast<unsigned short*>(bp + align_bp_bytes(T, R));
+    float* em = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(s_dyn) + align_trace_bytes(T, R));
+
+    // validation and feasibility: the rules (and codes) of ctc_loss_kernel
+    if (threadIdx.x == 0) s_code = (Lab < 0 || Lab > max_label) ? 2 : 0;
+    __syncthreads();
+    if (s_code == 0) {
+        bool bad = false;
+        for (int i = threadIdx.x; i < Lab; i += CTC_THREADS) {
+            const int v = labels[(size_t)b * max_label + i];
+            bad |= v < 0 || v >= blank;
+            s_lab[i] = v;
+            s_first[i] = -1;
+            s_end[i] = -1;
+        }
+        if (__syncthreads_or(bad) && threadIdx.x == 0) s_code = 3;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_code == 0) {
+        int reps = 0;
+        for (int i = 1; i < Lab; ++i) reps += s_lab[i] == s_lab[i - 1];
+        if (Lab + reps > L || L == 0) s_code = 1;
+    }
+    __syncthreads();
+    if (s_code != 0) {
+        if (threadIdx.x == 0) {
+            path_logp[b] = -INFINITY;
+            if (status) status[b] = s_code;
+            if (status_word)
+                __hip_atomic_fetch_or(status_word, 1u << s_code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        for (int t = threadIdx.x; t < T; t += CTC_THREADS) frame_state[(size_t)b * T + t] = -1;
+        for (int i = threadIdx.x; i < max_label; i += CTC_THREADS) {
+            reinterpret_cast<int2*>(span)[(size_t)b * max_label + i] = make_int2(-1, -1);
+            char_conf[(size_t)b * max_label + i] = 0.f;
+        }
+        return;
+    }
+    if (status && threadIdx.x == 0) status[b] = 0;
+
+    // log-sum-exp of every valid frame (for the outputs only) and, with LAT, the
+    // frame's emissions: a wave takes U frames with all of their loads in flight
+    constexpr int NW = CTC_THREADS / 64, NQ = CTC_MAX_C / 64, U = 8;
+    for (int t0 = wave; t0 < L; t0 += U * NW) {
+        float v[U][NQ];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 + u * NW;
+            const float* row = logits + ((size_t)t * B + b) * C;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const int k = lane + 64 * q;
+                v[u][q] = (t < L && k < C) ? row[k] : -INFINITY;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int t = t0 + u * NW;                   // wave-uniform
+            if (t >= L) continue;
+            float m = -INFINITY;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) m = fmaxf(m, v[u][q]);
+            m = wave_max_dpp(m);
+            float sum = 0.f;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q)
+                if (lane + 64 * q < C) sum += expf(v[u][q] - m);
+            sum = wave_sum_dpp(sum);
+            if (lane == 0) s_lse[t] = m + logf(sum);
+            if constexpr (LAT) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const int s = lane + 64 * r;
+                    const int k = s < S ? ((s & 1) ? s_lab[s >> 1] : blank) : blank;
+                    float val = 0.f;
+#pragma unroll
+                    for (int q = 0; q < NQ; ++q) {
+                        const float w = __shfl(v[u][q], k & 63, 64);
+                        if ((k >> 6) == q) val = w;
+                    }
+                    if (s < S) em[(size_t)t * S + s] = val;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    if (wave == 0) ctc_viterbi<R, LAT>(logits, em, s_lab, S, L, B, C, b, blank, bp, s_vend);
+    __syncthreads();
+
+    // backtrace, s[t - 1] = s[t] - bp[t][s[t]], in chunks of K frames. From any
+    // state below S a walk stays in [0, S) whatever the logits hold: one back
+    // is never taken at s = 0, two back only where s >= 3.
+    const int K = L <= 128 ? 8 : L <= 512 ? 16 : 32;
+    const int nch = (L + K - 1) / K;                    // chunk c: frames [c K, min(c K + K, L))
+    // (A) jump[c][s]: the state at frame c K - 1 of the path that is in s at chunk c's last frame
+    for (int i = threadIdx.x; i < (nch - 1) * S; i += CTC_THREADS) {
+        const int c = 1 + i / S;
+        int s = i % S;
+        const int s0 = s;
+        for (int t = min(c * K + K, L) - 1; t >= c * K; --t) s -= bp[(size_t)t * RS + s];
+        jump[(size_t)c * RS + s0] = (unsigned short)s;
+    }
+    __syncthreads();
+    // (B) the path's state at every chunk's last frame, from the end
+    if (threadIdx.x == 0) {
+        int s = (S >= 2 && s_vend[0] > s_vend[1]) ? S - 2 : S - 1;
+        s_cend[nch - 1] = (short)s;
+        for (int c = nch - 1; c >= 1; --c) {
+            s = jump[(size_t)c * RS + s];
+            s_cend[c - 1] = (short)s;
+        }
+    }
+    __syncthreads();
+    // (C) the path inside every chunk
+    if (threadIdx.x < nch) {
+        const int c = threadIdx.x;
+        int s = s_cend[c];
+        for (int t = min(c * K + K, L) - 1; t >= c * K; --t) {
+            s_path[t] = (short)s;
+            if (t > 0) s -= bp[(size_t)t * RS + s];
+        }
+    }
+    __syncthreads();
+    // a character's frames are one run of the path: its two ends write first / end
+    for (int t = threadIdx.x; t < L; t += CTC_THREADS) {
+        const int s = s_path[t];
+        if (s & 1) {
+            if (t == 0 || s_path[t - 1] != s) s_first[s >> 1] = t;
+            if (t == L - 1 || s_path[t + 1] != s) s_end[s >> 1] = t + 1;
+        }
+    }
+
+    for (int t = threadIdx.x; t < T; t += CTC_THREADS) frame_state[(size_t)b * T + t] = t < L ? (int)s_path[t] : -1;
+    // log-probability of the path: sum over its frames of logit - lse
+    float acc = 0.f;
+    for (int t = threadIdx.x; t < L; t += CTC_THREADS) {
+        const int s = s_path[t];
+        acc += align_em<LAT>(logits, em, t, S, s, (s & 1) ? s_lab[s >> 1] : blank, B, C, b) - s_lse[t];
+    }
+    acc = wave_sum_dpp(acc);
+    if (lane == 0) s_part[wave] = acc;
+    __syncthreads();                                    // s_first / s_end
+    // a character's confidence: its softmax probability at the best frame of its span
+    for (int i = threadIdx.x; i < max_label; i += CTC_THREADS) {
+        int f = -1, e = -1;
+        float conf = 0.f;
+        if (i < Lab) {
+            f = s_first[i];
+            e = s_end[i];
+            float m = -INFINITY;
+            for (int t = f; t < e && f >= 0; ++t)
+                m = fmaxf(m, align_em<LAT>(logits, em, t, S, 2 * i + 1, s_lab[i], B, C, b) - s_lse[t]);
+            conf = expf(m);
+        }
+        reinterpret_cast<int2*>(span)[(size_t)b * max_label + i] = make_int2(f, e);
+        char_conf[(size_t)b * max_label + i] = conf;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float tot = 0.f;
+        for (int w = 0; w < CTC_THREADS / 64; ++w) tot += s_part[w];
+        path_logp[b] = tot;
+    }
+}
+
 // ------------------------------------------------------------------- C ABI
+// registers per lane of the instantiation that serves max_label_len (1, 2, 4 or 8): a backpointer row is that wide
+static int align_regs(int max_label_len) {
+    const int R = (2 * max_label_len + 1 + 63) / 64;
+    return R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : 8;
+}
+
+extern "C" size_t ocrk_ctc_align_workspace_size(int T, int B, int max_label_len) {
+    if (T <= 0 || B <= 0 || max_label_len < 0 || 2 * max_label_len + 1 > 64 * CTC_MAX_R) return 0;
+    return (size_t)B * align_trace_bytes(T, align_regs(max_label_len));
+}
+
+extern "C" int ocrk_ctc_align(const float* logits, const int* labels, const int* label_len, const int* seq_len,
+                              int T, int B, int C, int max_label_len, int* frame_state, int* span,
+                              float* char_conf, float* path_logp, int* status, uint32_t* status_word, void* ws,
+                              size_t ws_bytes, void* stream) {
+    OCRK_REQUIRE(T > 0 && T <= CTC_MAX_T, "ocrk_ctc_align: T=%d out of range (1..%d)", T, CTC_MAX_T);
+    OCRK_REQUIRE(B >= 0 && C >= 2 && C <= CTC_MAX_C, "ocrk_ctc_align: bad B=%d / C=%d", B, C);
+    OCRK_REQUIRE(max_label_len >= 0 && 2 * max_label_len + 1 <= 64 * CTC_MAX_R,
+                 "ocrk_ctc_align: max_label_len=%d too long (<= %d)", max_label_len, (64 * CTC_MAX_R - 1) / 2);
+    OCRK_REQUIRE(ws_bytes >= ocrk_ctc_align_workspace_size(T, B, max_label_len),
+                 "ocrk_ctc_align: workspace too small");
+    if (B == 0) return OCRK_OK;
+    OCRK_REQUIRE(logits && labels && label_len && seq_len && frame_state && span && char_conf && path_logp && ws,
+                 "ocrk_ctc_align: null pointer");
+    OCRK_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 1) == 0 && (reinterpret_cast<uintptr_t>(span) & 7) == 0,
+                 "ocrk_ctc_align: ws must be 2-B and span 8-B aligned");
+    const int RR = align_regs(max_label_len);
+    hipStream_t s = ocrk::as_stream(stream);
+    const size_t dyn = align_trace_bytes(T, RR) + (size_t)T * (2 * (size_t)max_label_len + 1) * sizeof(float);
+    const bool in_lds = dyn <= ALIGN_LAT_MAX && ocrk::opt(ocrk::OPT_CTC_LDS) != 0;   // 0: backpointers in the workspace
+#define ALIGN_ARGS logits, labels, label_len, seq_len, T, B, C, max_label_len, frame_state, span, char_conf, path_logp, status, status_word, (unsigned char*)ws
+#define ALIGN_LAUNCH(N)                                                                                       \
+    do {                                                                                                      \
+        if (in_lds) {                                                                                         \
+            static ocrk::DeviceOnce attr;                                                                     \
+            ocrk::set_dyn_lds(attr, reinterpret_cast<const void*>(&ctc_align_kernel<N, true>), ALIGN_LAT_MAX); \
+            ctc_align_kernel<N, true><<<B, CTC_THREADS, dyn, s>>>(ALIGN_ARGS);                                \
+        } else {                                                                                              \
+            ctc_align_kernel<N, false><<<B, CTC_THREADS, 0, s>>>(ALIGN_ARGS);                                 \
+        }                                                                                                     \
+    } while (0)
+    if (RR == 1) ALIGN_LAUNCH(1);
+    else if (RR == 2) ALIGN_LAUNCH(2);
+    else if (RR == 4) ALIGN_LAUNCH(4);
+    else ALIGN_LAUNCH(8);
+#undef ALIGN_LAUNCH
+#undef ALIGN_ARGS
+    return ocrk::launch_status("ocrk_ctc_align");
+}
+
 extern "C" size_t ocrk_ctc_workspace_size(int T, int B, int max_label_len) {
     return (size_t)B * 2 * T * (2 * (size_t)max_label_len + 1) * sizeof(float);
 }

@@ -5,9 +5,12 @@ Mirrors the tf.nn / tf calls the reference makes on the hot path:
   * ctc_beam_search_decoder  -- src/weinman/test.py:84-88 (beam 128),
                                 src/weinman/client.py:227-231 (merge_repeated=False)
   * edit_distance            -- src/weinman/test.py:90 (normalize=False)
+ctc_alignment (with frame_center_px / frames_to_px) has no tf counterpart: it
+places a decoded string's characters on the frames, for server.Recognition.
 Sparse outputs are returned dense, -1 padded (what sparse_tensor_to_dense(-1)
 gives the reference, validate.py:91-92), plus per-row lengths.
 """
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -47,6 +50,56 @@ def ctc_beam_search_decoder_raw(inputs, sequence_length, beam_width=100, top_pat
     [top_paths, B, T], out_len [top_paths, B], log_probability)."""
     return K.ctc_beam_decode(_f32(inputs), sequence_length.to(torch.int32).contiguous(), beam_width,
                              top_paths, merge_repeated)
+
+
+def _masked_labels(labels, label_length):
+    """Dense i32 labels with every position at or past its row's length set to
+    0: the decoders pad with -1, which must never reach a kernel as a label."""
+    lab = labels.to(torch.int32)
+    if lab.dim() == 1:
+        lab = lab.reshape(lab.shape[0], 0)
+    ln = label_length.to(torch.int32).contiguous()
+    pos = torch.arange(lab.shape[1], device=lab.device, dtype=torch.int32)
+    return torch.where(pos[None, :] < ln[:, None], lab, torch.zeros_like(lab)).contiguous(), ln
+
+
+def ctc_alignment(inputs, labels, label_length, sequence_length):
+    """The best single path of each row's label through its logits (no
+    reference counterpart: what src/processing needs to place and filter the
+    recognised characters). inputs [T, B, C]; labels dense [B, W] as either
+    decoder returns them (-1 padded, any integer dtype) with label_length [B];
+    sequence_length [B]. Returns (frame_state i32 [B, T] extended-state index
+    per frame, -1 past the sequence; span i32 [B, W, 2] (first, end) frames of
+    each character; char_conf f32 [B, W]; path_logp f32 [B]; status i32 [B],
+    0 = aligned, else the ctc_loss codes and all outputs void)."""
+    lab, ln = _masked_labels(labels, label_length)
+    return K.ctc_align(_f32(inputs), lab, ln, sequence_length.to(torch.int32).contiguous())
+
+
+# Where a frame sits in the crop (src/weinman/model.py:134-163), in input-column
+# indices (column c spans c - 0.5 .. c + 0.5). The 3x3 convolutions are 'same'
+# except conv1, which is 'valid' and trims one column per side: its column j is
+# centred on input column j + 1. pool2 (width 2, stride 2) makes column p from
+# conv columns 2p, 2p + 1: centre 2p + 1.5. pool4 and pool6 are width-2,
+# stride-1 windows, each moving the centre half a column of its input, i.e. one
+# input column: pool4 column q sits at 2q + 2.5 and pool6 column t, the frame,
+# at 2t + 3.5 (pool8 pools rows only). Frames are 2 input columns apart, so
+# frame t owns 2t + 2.5 .. 2t + 4.5. Cross-check with model.py:152-163's
+# T = floor((W - 2) / 2) - 2: for even W the last centre is W - 4.5, the mirror
+# of the first (3.5) about the crop's middle (W - 1) / 2; W = 256 gives 3.5 and 251.5.
+def frame_center_px(t):
+    """Input column on which frame t's pooling footprint is centred."""
+    return 2.0 * t + 3.5
+
+
+def frames_to_px(first, end, width):
+    """Input-column extent (x0, x1) of the frames [first, end), clipped to
+    [0, width]. Scalars give floats; NumPy arrays (broadcast) give arrays."""
+    x0 = np.clip(2.0 * np.asarray(first) + 2.5, 0.0, width)
+    x1 = np.clip(2.0 * np.asarray(end) + 2.5, 0.0, width)
+    if x0.ndim == 0 and x1.ndim == 0:
+        return float(x0), float(x1)
+    return x0, x1
 
 
 def edit_distance(hypothesis, hypothesis_len, truth, truth_len, totals=None):

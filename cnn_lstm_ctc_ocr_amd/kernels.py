@@ -956,6 +956,36 @@ def ctc_loss(logits, labels, label_len, seq_len, grad_scale=1.0, need_grad=True,
     return loss, grad, status
 
 
+def ctc_align(logits, labels, label_len, seq_len, status=None):
+    """Best single path of each label through the logits (ocrk_ctc_align).
+
+    logits f32 [T,B,C]; labels i32 [B,Lmax]; label_len, seq_len i32 [B].
+    Returns (frame_state i32 [B,T], span i32 [B,Lmax,2], char_conf f32 [B,Lmax],
+    path_logp f32 [B], status i32 [B])."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_align takes float32 logits")
+    _chk(logits, labels, label_len, seq_len)
+    T, B, C = logits.shape
+    Lmax = Lout = labels.shape[1] if labels.dim() == 2 else 0
+    labels = labels.reshape(B, Lmax)
+    if labels.numel() == 0:
+        labels = torch.zeros(B, 1, dtype=torch.int32, device=logits.device)
+        Lmax = 1
+    nb = _lib.lib().ocrk_ctc_align_workspace_size(T, B, Lmax)
+    ws = _ws(nb, logits.device)
+    dev = logits.device
+    frame_state = torch.empty(B, T, dtype=torch.int32, device=dev)
+    span = torch.empty(B, Lmax, 2, dtype=torch.int32, device=dev)
+    char_conf = torch.empty(B, Lmax, dtype=torch.float32, device=dev)
+    path_logp = torch.empty(B, dtype=torch.float32, device=dev)
+    if status is None:
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_align", ptr(logits), ptr(labels), ptr(label_len), ptr(seq_len), T, B, C, Lmax,
+         ptr(frame_state), ptr(span), ptr(char_conf), ptr(path_logp), ptr(status), ptr(status_word(dev)),
+         ptr(ws), nb, _stream(logits))
+    return frame_state, span[:, :Lout], char_conf[:, :Lout], path_logp, status
+
+
 def ctc_greedy_decode(logits, seq_len, merge_repeated=True):
     """Greedy decode. Returns (out i64 [B,T] -1 padded, out_len i32 [B], neg_sum f32 [B])."""
     if logits.dtype != torch.float32:

@@ -22,13 +22,16 @@ The model step runs on the GPU: convnet_layers(INFER) -> rnn_layers ->
 ctc_greedy_decoder (server.py:83-89), or the beam-search decoder when the
 service is built with decoder="beam" (BASELINE config C5, beam 16).
 """
+import math
 import queue
 import time
+from typing import NamedTuple, Tuple
 
 import numpy as np
 import torch
 
-from . import decode, validate
+from . import _lib, decode, validate
+from . import kernels as K
 from .config import INFER
 from .model import convnet_layers, rnn_layers
 from .mjsynth import num_classes
@@ -92,6 +95,15 @@ def fill_batch(infos, batch, widths, bucket_size):
     return list(infos) + [("-1", "0")] * extra, batch, widths
 
 
+class Recognition(NamedTuple):
+    """What Recognizer(detail=True) returns per crop (a plain tuple of built-in
+    values: it crosses ReplicaPool's and a Manager's queues pickled)."""
+    text: str
+    confidence: float                              # posterior of the string: exp(-ctc_loss(text | logits))
+    char_confidence: Tuple[float, ...]             # per character: its best softmax probability inside its span
+    char_px: Tuple[Tuple[float, float], ...]       # per character: (x0, x1) input columns, within [0, width]
+
+
 class Recognizer:
     """The per-batch model step of LocalServer.run (server.py:80-89, 132-138):
     uint8 [bs, 32, W, 1] + widths -> one string per crop. Holds the variables
@@ -101,10 +113,15 @@ class Recognizer:
     store gives the reference's strings (greedy and beam decodes are identical
     to the oracle's on the golden MJSynth batch; bf16 differs, CER 0.034 greedy /
     0.022 beam-16 there -- bench.py's cer_vs_ref). A bf16 store is refused
-    unless allow_bf16=True states that approximate strings are acceptable."""
+    unless allow_bf16=True states that approximate strings are acceptable.
+
+    detail=True: __call__ returns a Recognition per crop instead of a string --
+    the same text, its posterior, and each character's confidence and pixel
+    extent from the forced alignment of the decoded labels to the same logits
+    (decode.ctc_alignment; two more launches per batch, none when False)."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
-                 graphs=False):
+                 graphs=False, detail=False):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -115,6 +132,7 @@ class Recognizer:
         self.beam_width = beam_width
         self.merge_repeated = merge_repeated
         self.graphs = {} if graphs else None      # (bs, W) -> infer.InferGraph
+        self.detail = bool(detail)
 
     def _graphed(self, batch, widths):
         key = tuple(batch.shape)
@@ -149,13 +167,70 @@ class Recognizer:
             out, _ = decode.ctc_beam_search_decoder(logits, seq_len, self.beam_width, 1, self.merge_repeated)
             return out[0]
 
+    def _decoded(self, batch, widths):
+        """(logits [T, bs, C], seq_len [bs], out i64 [bs, T] (labels then -1),
+        out_len i32 [bs]): the launches of labels(), keeping what the alignment needs."""
+        dev = self.store.device
+        if self.graphs is not None:
+            g = self._graphed(batch, widths)
+            logits, seq_len = g.logits, g.seq_len
+            if self.decoder == "greedy":
+                return logits, seq_len, g.decoded, g.decoded_len
+        else:
+            with torch.no_grad():
+                image = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
+                width = torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+                features, seq_len = convnet_layers(image, width, INFER, self.store)
+                logits = rnn_layers(features, seq_len, num_classes(), self.store)
+            if self.decoder == "greedy":
+                out, out_len, _ = decode.ctc_greedy_decoder_raw(logits, seq_len, self.merge_repeated)
+                return logits, seq_len, out, out_len
+        out, out_len, _ = decode.ctc_beam_search_decoder_raw(logits, seq_len, self.beam_width, 1, self.merge_repeated)
+        return logits, seq_len, out[0], out_len[0]
+
+    def recognitions(self, batch, widths):
+        """One Recognition per crop. A row whose decode cannot be aligned (only
+        a greedy decode with merge_repeated=False can be infeasible: 'aa' read
+        from two adjacent frames) keeps its text with confidence 0.0, zero
+        character confidences and (0.0, 0.0) extents; the CTC bits such a row
+        sets in the device status word are cleared here."""
+        logits, seq_len, out, out_len = self._decoded(batch, widths)
+        with torch.no_grad():
+            n_max = int(out_len.max().item()) if out_len.numel() else 0
+            lab, ln = decode._masked_labels(out[:, :n_max], out_len)
+            logits = decode._f32(logits)
+            seq = seq_len.to(torch.int32).contiguous()
+            _fs, span, conf, _logp, status = K.ctc_align(logits, lab, ln, seq)
+            loss, _, _ = K.ctc_loss(logits, lab, ln, seq, need_grad=False)
+            # two read-backs (one per dtype), then whole-array host work: a crop costs no per-character NumPy call
+            ints = torch.cat([lab, span.reshape(lab.shape[0], -1), ln[:, None], status[:, None]], dim=1).cpu().numpy()
+            flts = torch.cat([conf, loss[:, None]], dim=1).cpu().numpy()
+        lab, span = ints[:, :n_max], ints[:, n_max:3 * n_max].reshape(-1, n_max, 2)
+        ln, status = ints[:, -2].tolist(), ints[:, -1].tolist()
+        if any(status):
+            K.clear_status(self.store.device, _lib.STATUS_CTC)
+        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], np.asarray(widths, np.float64)[:, None])
+        px = np.stack([x0, x1], axis=2).tolist()
+        conf, loss, lab = flts[:, :n_max].tolist(), flts[:, -1].tolist(), lab.tolist()
+        res = []
+        for b, n in enumerate(ln):
+            text = validate._get_string(lab[b][:n])
+            if status[b] != 0:
+                res.append(Recognition(text, 0.0, (0.0,) * n, ((0.0, 0.0),) * n))
+                continue
+            res.append(Recognition(text, math.exp(-loss[b]), tuple(conf[b][:n]), tuple(map(tuple, px[b][:n]))))
+        return res
+
     def __call__(self, batch, widths):
+        if self.detail:
+            return self.recognitions(batch, widths)
         return validate.decode_strings(self.labels(batch, widths))
 
 
 class LocalServer:
     """server.py:59-145. `recognizer` is a Recognizer (or any callable
-    (batch, widths) -> list of strings); queues come from `manager` (a
+    (batch, widths) -> list of strings, or of Recognition tuples with
+    Recognizer(detail=True): results are forwarded as they are); queues come from `manager` (a
     multiprocessing Manager, or None for in-process queue.Queue)."""
 
     def __init__(self, recognizer, manager=None, bucket_size=16, bucket_max_time=1.0, accept_narrow=False):
@@ -288,17 +363,18 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
     outq.put(("exit", rank, None))
 
 
-def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False):
+def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
+                   detail=False):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
     reference initialisers with `seed`). Picklable (spawn)."""
-    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16)
+    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail)
 
 
 class _GpuRecognizerFactory:
-    def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False):
+    def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
-        self.allow_bf16 = allow_bf16
+        self.allow_bf16, self.detail = allow_bf16, detail
 
     def __call__(self, device):
         from .config import ModelConfig
@@ -307,7 +383,8 @@ class _GpuRecognizerFactory:
         if self.checkpoint:
             from . import checkpoint as ckpt
             ckpt.restore(store, self.checkpoint)
-        return Recognizer(store, decoder=self.decoder, beam_width=self.beam_width, allow_bf16=self.allow_bf16)
+        return Recognizer(store, decoder=self.decoder, beam_width=self.beam_width, allow_bf16=self.allow_bf16,
+                          detail=self.detail)
 
 
 class ReplicaError(RuntimeError):

@@ -126,6 +126,29 @@ int ocrk_ctc_loss(const float* logits, const int* labels, const int* label_len, 
                   int T, int B, int C, int max_label_len, float grad_scale, float* loss, float* grad,
                   int* status, unsigned* status_word, void* ws, size_t ws_bytes, void* stream);
 
+/* Forced alignment of a label to the logits (added within v7; no reference graph op: the
+ * reference's src/processing and src/extract_fields place and filter the recognised lines on
+ * the host). The best single path (Viterbi) through the extended label
+ * l' = [blank, l0, blank, l1, ..., blank] over the first L = clamp(seq_len, 0, T) frames,
+ * maximising the sum of the RAW float32 logits along it (the frame log-sum-exp cannot change
+ * the argmax): V[t][s] = best + logit(t, l'_s), one float32 add, where best is V[t-1][s],
+ * replaced by V[t-1][s-1] only if strictly greater, then by V[t-1][s-2] only if that skip is
+ * allowed (s odd, s >= 3, l'_s != l'_{s-2}) and strictly greater; the path ends in state
+ * S-1 unless V[L-1][S-2] is strictly greater. Inputs, limits, validation, per-row status
+ * codes and status-word bits are those of ocrk_ctc_loss.
+ *   frame_state i32 [B][T]: the extended-state index of each frame (-1 for t >= L)
+ *   span        i32 [B][max_label_len][2]: (first, last + 1) frame of each label symbol
+ *               ((-1, -1) for i >= label_len); 8-B aligned
+ *   char_conf   f32 [B][max_label_len]: max over the span of softmax(logits[t])[l_i] (0 past the label)
+ *   path_logp   f32 [B]: sum over the path of log softmax (natural log)
+ * A row that cannot be aligned: frame_state -1, spans -1, char_conf 0, path_logp -inf.
+ *   ws: >= ocrk_ctc_align_workspace_size(T, B, max_label_len) bytes, 2-B aligned */
+size_t ocrk_ctc_align_workspace_size(int T, int B, int max_label_len);
+int ocrk_ctc_align(const float* logits, const int* labels, const int* label_len, const int* seq_len,
+                   int T, int B, int C, int max_label_len, int* frame_state, int* span, float* char_conf,
+                   float* path_logp, int* status, uint32_t* status_word, void* ws, size_t ws_bytes,
+                   void* stream);
+
 /* a10 -- validate._get_output (src/weinman/validate.py:81-92) =
  * tf.nn.ctc_greedy_decoder(logits, seq_len, merge_repeated) + sparse_to_dense(-1):
  *   out i64 [B, T] (labels then -1), out_len i32 [B], neg_sum_logits f32 [B] or NULL. */
