@@ -45,6 +45,9 @@ SIGNATURES = {
     "ocrk_ctc_loss": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _p, _sz, _p],
     "ocrk_ctc_align_workspace_size": [_i32, _i32, _i32],
     "ocrk_ctc_align": [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
+    "ocrk_ctc_lexicon_workspace_size": [_i32, _i32, _i32, _i32, _i32],
+    "ocrk_ctc_lexicon_score": [_p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz,
+                               _p],
     "ocrk_ctc_greedy_decode": [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "ocrk_ctc_beam_workspace_size": [_i32, _i32, _i32],
     "ocrk_gru_fwd_step": [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p],

@@ -20,52 +20,9 @@
 // The 16 waves serve the per-frame passes, which are latency chains
 // (measured at T=125, B=256, C=96: 43 us with the gradient vs 96 us for the
 // 256-thread, natural-log, global-reread form).
-#include <cfloat>
-
-#include "common.h"
+#include "ctc_lattice.h"                // lse2b / lse3b, the register-lattice shifts, CTC_MAX_*
 
 #define CTC_THREADS 1024            // 16 waves: the per-frame passes (log-sum-exp, occupations, gradient) are latency chains; measured 43 vs 75 us at 256
-#define CTC_MAX_R 8                 // S <= 512  (labels up to 255 symbols)
-#define CTC_MAX_T 4096
-#define CTC_MAX_C 256
-
-// The lattices and emissions hold log2 probabilities: the log-sum-exps are
-// then v_exp_f32 / v_log_f32 (base-2 hardware transcendentals, one
-// instruction each) instead of the libm expf / logf sequences, on the
-// recursion's serial chain. The -FLT_MAX floor keeps an all -inf argument
-// list NaN-free without a branch (2^-inf = 0, log2 0 = -inf).
-constexpr float LOG2E_F = 1.4426950408889634f, LN2_F = 0.6931471805599453f;
-__device__ __forceinline__ float lse2b(float a, float b) {
-    const float m = fmaxf(fmaxf(a, b), -FLT_MAX);
-    return m + __builtin_amdgcn_logf(__builtin_amdgcn_exp2f(a - m) + __builtin_amdgcn_exp2f(b - m));
-}
-__device__ __forceinline__ float lse3b(float a, float b, float c) {
-    const float m = fmaxf(fmaxf(fmaxf(a, b), c), -FLT_MAX);
-    return m + __builtin_amdgcn_logf(__builtin_amdgcn_exp2f(a - m) + __builtin_amdgcn_exp2f(b - m) +
-                                     __builtin_amdgcn_exp2f(c - m));
-}
-
-// value of register r at lane-1 (state s-1), across the register boundary.
-__device__ __forceinline__ float shift_up1(const float* a, int r, int lane) {
-    float v = __shfl_up(a[r], 1, 64);
-    float w = __shfl(a[r > 0 ? r - 1 : 0], 63, 64);
-    return lane == 0 ? (r > 0 ? w : -INFINITY) : v;
-}
-__device__ __forceinline__ float shift_up2(const float* a, int r, int lane) {
-    float v = __shfl_up(a[r], 2, 64);
-    float w = __shfl(a[r > 0 ? r - 1 : 0], 62 + lane, 64);
-    return lane < 2 ? (r > 0 ? w : -INFINITY) : v;
-}
-__device__ __forceinline__ float shift_dn1(const float* a, int r, int R, int lane) {
-    float v = __shfl_down(a[r], 1, 64);
-    float w = __shfl(a[r + 1 < R ? r + 1 : r], 0, 64);
-    return lane == 63 ? (r + 1 < R ? w : -INFINITY) : v;
-}
-__device__ __forceinline__ float shift_dn2(const float* a, int r, int R, int lane) {
-    float v = __shfl_down(a[r], 2, 64);
-    float w = __shfl(a[r + 1 < R ? r + 1 : r], lane - 62, 64);
-    return lane >= 62 ? (r + 1 < R ? w : -INFINITY) : v;
-}
 
 // Emission log-probabilities of the extended label, em[t*S + s] =
 // logit(t, l'_s) - lse(t): with LAT they are precomputed into LDS (every
@@ -73,19 +30,7 @@ __device__ __forceinline__ float shift_dn2(const float* a, int r, int R, int lan
 // LDS instead of waiting on a global load per step; without LAT (lattices too
 // large for LDS) they are read from the logits in the loop, as before. The
 // values are the same fp32 expressions either way.
-// Whole-wave DPP shifts (GFX9 wave_shr:1 / wave_shl:1): lane i takes lane i-1
-// (resp. i+1); the lane shifted in gets -inf. Used when the lattice fits one
-// register (S <= 64) instead of ds_bpermute shuffles on the recursion's
-// critical path.
-__device__ __forceinline__ float wave_shr1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -INFINITY),
-                                                                 __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_shl1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -INFINITY),
-                                                                 __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
-}
-
+//
 // Emission of state slot r at frame t, log2 units: from the LDS table (LAT)
 // or from the logits.
 template <bool LAT>

@@ -7,6 +7,9 @@ Mirrors the tf.nn / tf calls the reference makes on the hot path:
   * edit_distance            -- src/weinman/test.py:90 (normalize=False)
 ctc_alignment (with frame_center_px / frames_to_px) has no tf counterpart: it
 places a decoded string's characters on the frames, for server.Recognition.
+Lexicon / ctc_lexicon_decoder have none either: they score a closed word list
+against the logits (what src/extract_fields and src/accuracy_measure do on the
+host with fuzzy matches of the decoded string), for server.LexiconRecognition.
 Sparse outputs are returned dense, -1 padded (what sparse_tensor_to_dense(-1)
 gives the reference, validate.py:91-92), plus per-row lengths.
 """
@@ -14,6 +17,9 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from . import mjsynth
+
+MAX_WORD_LEN = 255                                          # the CTC kernels' label limit
 
 
 def _f32(logits):
@@ -74,6 +80,71 @@ def ctc_alignment(inputs, labels, label_length, sequence_length):
     0 = aligned, else the ctc_loss codes and all outputs void)."""
     lab, ln = _masked_labels(labels, label_length)
     return K.ctc_align(_f32(inputs), lab, ln, sequence_length.to(torch.int32).contiguous())
+
+
+class Lexicon:
+    """An ordered closed vocabulary: strings over mjsynth.out_charset, encoded
+    once (mjsynth.encode) and kept as dense int32 labels + lengths per device.
+    ValueError for an empty list, an empty string, a character outside the
+    charset, a duplicate, or a word over 255 characters. Pickles as its plain
+    list of strings (the device tensors are rebuilt where it lands)."""
+
+    def __init__(self, words):
+        words = list(words)
+        if not words:
+            raise ValueError("Lexicon: the word list is empty")
+        seen = set()
+        encoded = []
+        for i, w in enumerate(words):
+            if not isinstance(w, str):
+                raise ValueError(f"Lexicon: entry {i} is {type(w).__name__}, not a string")
+            if not w:
+                raise ValueError(f"Lexicon: entry {i} is the empty string")
+            if len(w) > MAX_WORD_LEN:
+                raise ValueError(f"Lexicon: entry {i} has {len(w)} characters (at most {MAX_WORD_LEN})")
+            if w in seen:
+                raise ValueError(f"Lexicon: duplicate word {w!r} (entry {i})")
+            seen.add(w)
+            try:
+                encoded.append(mjsynth.encode(w))
+            except ValueError:
+                bad = next(ch for ch in w if ch not in mjsynth.out_charset)
+                raise ValueError(f"Lexicon: {w!r} (entry {i}) has the character {bad!r} outside the charset") from None
+        self.words = tuple(words)
+        self.lengths = np.array([len(e) for e in encoded], np.int32)
+        self.labels = np.zeros((len(encoded), int(self.lengths.max())), np.int32)
+        for i, e in enumerate(encoded):
+            self.labels[i, :len(e)] = e
+        self._device = {}
+
+    def __len__(self):
+        return len(self.words)
+
+    def __reduce__(self):
+        return (Lexicon, (list(self.words),))
+
+    def tensors(self, device):
+        """(labels i32 [n, max_len], lengths i32 [n]) on `device`, uploaded once per device."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = (torch.from_numpy(self.labels).to(device),
+                                     torch.from_numpy(self.lengths).to(device))
+        return t
+
+
+def ctc_lexicon_decoder(inputs, sequence_length, lexicon, top_k=1):
+    """The top_k words of `lexicon` for each row of inputs [T, B, C] by
+    log p(word | inputs[:sequence_length[b], b]) (the CTC sum over all paths,
+    -ctc_loss), ties to the earlier word. Returns (index i32 [B, top_k] into
+    lexicon.words, -1 where fewer than top_k words fit the row; log_probability
+    f32 [B, top_k], -inf there; log_norm f32 [B], the log-sum-exp over the whole
+    lexicon: exp(log_probability - log_norm) is the posterior within it).
+    Device tensors, no host sync."""
+    lab, ln = lexicon.tensors(inputs.device)
+    _logp, idx, logp, log_norm, _status = K.ctc_lexicon_score(
+        _f32(inputs), sequence_length.to(torch.int32).contiguous(), lab, ln, top_k, need_scores=False)
+    return idx, logp, log_norm
 
 
 # Where a frame sits in the crop (src/weinman/model.py:134-163), in input-column

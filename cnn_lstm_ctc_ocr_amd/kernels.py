@@ -986,6 +986,39 @@ def ctc_align(logits, labels, label_len, seq_len, status=None):
     return frame_state, span[:, :Lout], char_conf[:, :Lout], path_logp, status
 
 
+def ctc_lexicon_score(logits, seq_len, words, word_len, top_k=1, need_scores=True):
+    """log p(word | logits) of every word of a list for every row, and the best of them
+    (ocrk_ctc_lexicon_score).
+
+    logits f32 [T,B,C]; seq_len i32 [B]; words i32 [K,Wmax] (dense, padded); word_len i32 [K].
+    Returns (logp f32 [B,K] or None without need_scores, top_idx i32 [B,top_k] (-1 padded),
+    top_logp f32 [B,top_k] (-inf padded), log_norm f32 [B], word_status i32 [K]: 0 ok,
+    2 bad length, 3 bad label value). A word too long for a row scores -inf there and
+    sets no status bit."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_lexicon_score takes float32 logits")
+    if words.dim() != 2 or word_len.dim() != 1 or words.shape[0] != word_len.shape[0]:
+        raise ValueError("ctc_lexicon_score takes words [K, Wmax] and word_len [K]")
+    if words.dtype != torch.int32 or word_len.dtype != torch.int32 or seq_len.dtype != torch.int32:
+        raise TypeError("ctc_lexicon_score takes int32 words, word_len and seq_len")
+    _chk(logits, seq_len, words, word_len)
+    T, B, C = logits.shape
+    n_words, Wmax = words.shape
+    top_k = int(top_k)
+    dev = logits.device
+    nb = _lib.lib().ocrk_ctc_lexicon_workspace_size(T, B, C, n_words, Wmax)
+    ws = _ws(nb, dev)
+    logp = torch.empty(B, n_words, dtype=torch.float32, device=dev) if need_scores else None
+    top_idx = torch.empty(B, max(top_k, 0), dtype=torch.int32, device=dev)
+    top_logp = torch.empty(B, max(top_k, 0), dtype=torch.float32, device=dev)
+    log_norm = torch.empty(B, dtype=torch.float32, device=dev)
+    word_status = torch.empty(n_words, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_lexicon_score", ptr(logits), ptr(seq_len), T, B, C, ptr(words), ptr(word_len), n_words, Wmax,
+         top_k, ptr(logp), ptr(top_idx), ptr(top_logp), ptr(log_norm), ptr(word_status), ptr(status_word(dev)),
+         ptr(ws), nb, _stream(logits))
+    return logp, top_idx, top_logp, log_norm, word_status
+
+
 def ctc_greedy_decode(logits, seq_len, merge_repeated=True):
     """Greedy decode. Returns (out i64 [B,T] -1 padded, out_len i32 [B], neg_sum f32 [B])."""
     if logits.dtype != torch.float32:

@@ -25,6 +25,7 @@ service is built with decoder="beam" (BASELINE config C5, beam 16).
 import math
 import queue
 import time
+from collections.abc import Sequence
 from typing import NamedTuple, Tuple
 
 import numpy as np
@@ -104,6 +105,18 @@ class Recognition(NamedTuple):
     char_px: Tuple[Tuple[float, float], ...]       # per character: (x0, x1) input columns, within [0, width]
 
 
+class LexiconRecognition(NamedTuple):
+    """What Recognizer(lexicon=..., detail=True) returns per crop (built-in values only,
+    like Recognition). A crop no word of the lexicon fits (too narrow for all of them) has
+    text "", confidence and posterior 0.0 and empty tuples."""
+    text: str                                      # the lexicon's best word for the crop
+    confidence: float                              # exp(-ctc_loss(text | logits)), Recognition.confidence's meaning
+    lexicon_posterior: float                       # p(text) / sum of p(word) over the lexicon
+    alternatives: Tuple[Tuple[str, float], ...]    # up to lexicon_top (word, log p), best first; [0] is text
+    char_confidence: Tuple[float, ...]             # as Recognition, from the alignment of text
+    char_px: Tuple[Tuple[float, float], ...]
+
+
 class Recognizer:
     """The per-batch model step of LocalServer.run (server.py:80-89, 132-138):
     uint8 [bs, 32, W, 1] + widths -> one string per crop. Holds the variables
@@ -118,10 +131,16 @@ class Recognizer:
     detail=True: __call__ returns a Recognition per crop instead of a string --
     the same text, its posterior, and each character's confidence and pixel
     extent from the forced alignment of the decoded labels to the same logits
-    (decode.ctc_alignment; two more launches per batch, none when False)."""
+    (decode.ctc_alignment; two more launches per batch, none when False).
+
+    lexicon (a decode.Lexicon or a sequence of strings): closed-vocabulary
+    recognition. __call__ returns each crop's most probable lexicon word by
+    log p(word | logits) (decode.ctc_lexicon_decoder; "" where no word fits the
+    crop) and the unconstrained decoder is not launched; with detail=True a
+    LexiconRecognition with the best lexicon_top words."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
-                 graphs=False, detail=False):
+                 graphs=False, detail=False, lexicon=None, lexicon_top=1):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -131,16 +150,27 @@ class Recognizer:
         self.decoder = decoder
         self.beam_width = beam_width
         self.merge_repeated = merge_repeated
-        self.graphs = {} if graphs else None      # (bs, W) -> infer.InferGraph
+        self.graphs = {} if graphs else None      # batch shape (+ "logits": no decoder) -> infer.InferGraph
         self.detail = bool(detail)
+        if lexicon is not None and not isinstance(lexicon, decode.Lexicon):
+            if isinstance(lexicon, str) or not isinstance(lexicon, Sequence):
+                raise TypeError("Recognizer: lexicon is a decode.Lexicon or a sequence of strings, "
+                                f"not {type(lexicon).__name__}")
+            lexicon = decode.Lexicon(lexicon)
+        if not 1 <= int(lexicon_top) <= 32:
+            raise ValueError("Recognizer: lexicon_top is 1..32")
+        self.lexicon = lexicon
+        self.lexicon_top = int(lexicon_top)
 
-    def _graphed(self, batch, widths):
-        key = tuple(batch.shape)
+    def _graphed(self, batch, widths, decoded=True):
+        """decoded=False: the forward alone (the lexicon path launches no unconstrained decoder)."""
+        shape = tuple(batch.shape)
+        key = shape if decoded else shape + ("logits",)
         g = self.graphs.get(key)
         if g is None or g.version != self.store.version:
             from .infer import InferGraph
-            g = self.graphs[key] = InferGraph(self.store, batch=key[0], width=key[2],
-                                              decoder="greedy" if self.decoder == "greedy" else None,
+            g = self.graphs[key] = InferGraph(self.store, batch=shape[0], width=shape[2],
+                                              decoder="greedy" if decoded and self.decoder == "greedy" else None,
                                               merge_repeated=self.merge_repeated)
         return g.run(torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)),
                      torch.from_numpy(np.asarray(widths, np.int32)))
@@ -221,7 +251,71 @@ class Recognizer:
             res.append(Recognition(text, math.exp(-loss[b]), tuple(conf[b][:n]), tuple(map(tuple, px[b][:n]))))
         return res
 
+    def _lexicon_top(self, batch, widths, top_k):
+        """(logits f32 [T, bs, C], seq_len i32 [bs], index [bs, top_k], log p [bs, top_k], log_norm [bs]):
+        the forward (the replayed graph's, with graphs=True) and the lexicon scoring on its logits."""
+        if self.graphs is not None:
+            g = self._graphed(batch, widths, decoded=False)
+            logits, seq_len = g.logits, g.seq_len
+        else:
+            dev = self.store.device
+            with torch.no_grad():
+                image = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
+                width = torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+                features, seq_len = convnet_layers(image, width, INFER, self.store)
+                logits = rnn_layers(features, seq_len, num_classes(), self.store)
+        with torch.no_grad():
+            logits = decode._f32(logits)
+            seq = seq_len.to(torch.int32).contiguous()
+            idx, logp, log_norm = decode.ctc_lexicon_decoder(logits, seq, self.lexicon, top_k)
+        return logits, seq, idx, logp, log_norm
+
+    def lexicon_words(self, batch, widths):
+        """The most probable lexicon word per crop ("" where no word fits the crop's frames)."""
+        idx = self._lexicon_top(batch, widths, 1)[2]
+        words = self.lexicon.words
+        return [words[i] if i >= 0 else "" for i in idx[:, 0].tolist()]
+
+    def lexicon_recognitions(self, batch, widths):
+        """One LexiconRecognition per crop: the lexicon_top best words, and the best one
+        aligned to the logits as recognitions() aligns the decoded string."""
+        logits, seq, idx, logp, log_norm = self._lexicon_top(batch, widths, self.lexicon_top)
+        k = self.lexicon_top
+        with torch.no_grad():
+            lab_all, ln_all = self.lexicon.tensors(logits.device)
+            found = idx[:, 0] >= 0
+            best = idx[:, 0].clamp(min=0).long()
+            lab = lab_all[best].contiguous()
+            ln = torch.where(found, ln_all[best], torch.zeros_like(ln_all[best])).contiguous()
+            _fs, span, conf, _logp, status = K.ctc_align(logits, lab, ln, seq)
+            n_max = lab.shape[1]
+            ints = torch.cat([idx, span.reshape(lab.shape[0], -1), ln[:, None], status[:, None]], dim=1).cpu().numpy()
+            flts = torch.cat([logp, log_norm[:, None], conf], dim=1).cpu().numpy()
+        idx, span = ints[:, :k].tolist(), ints[:, k:k + 2 * n_max].reshape(-1, n_max, 2)
+        ln, status = ints[:, -2].tolist(), ints[:, -1].tolist()
+        if any(status):                                     # a row without a word and without frames (seq_len 0)
+            K.clear_status(self.store.device, _lib.STATUS_CTC)
+        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], np.asarray(widths, np.float64)[:, None])
+        px = np.stack([x0, x1], axis=2).tolist()
+        logp, log_norm, conf = flts[:, :k].tolist(), flts[:, k].tolist(), flts[:, k + 1:].tolist()
+        words = self.lexicon.words
+        res = []
+        for b, n in enumerate(ln):
+            if idx[b][0] < 0:
+                res.append(LexiconRecognition("", 0.0, 0.0, (), (), ()))
+                continue
+            alts = tuple((words[i], lp) for i, lp in zip(idx[b], logp[b]) if i >= 0)
+            if status[b] != 0:
+                cc, cp = (0.0,) * n, ((0.0, 0.0),) * n
+            else:
+                cc, cp = tuple(conf[b][:n]), tuple(map(tuple, px[b][:n]))
+            res.append(LexiconRecognition(words[idx[b][0]], math.exp(logp[b][0]), math.exp(logp[b][0] - log_norm[b]),
+                                          alts, cc, cp))
+        return res
+
     def __call__(self, batch, widths):
+        if self.lexicon is not None:
+            return self.lexicon_recognitions(batch, widths) if self.detail else self.lexicon_words(batch, widths)
         if self.detail:
             return self.recognitions(batch, widths)
         return validate.decode_strings(self.labels(batch, widths))
@@ -364,17 +458,22 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
 
 
 def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
-                   detail=False):
+                   detail=False, lexicon=None, lexicon_top=1):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
-    reference initialisers with `seed`). Picklable (spawn)."""
-    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail)
+    reference initialisers with `seed`). Picklable (spawn); a lexicon travels
+    as its plain list of strings and is encoded in the replica."""
+    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top)
 
 
 class _GpuRecognizerFactory:
-    def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False):
+    def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False, lexicon=None,
+                 lexicon_top=1):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
         self.allow_bf16, self.detail = allow_bf16, detail
+        if lexicon is not None:                             # checked here, in the parent; pickled as strings
+            lexicon = list(decode.Lexicon(lexicon).words if not isinstance(lexicon, decode.Lexicon) else lexicon.words)
+        self.lexicon, self.lexicon_top = lexicon, lexicon_top
 
     def __call__(self, device):
         from .config import ModelConfig
@@ -384,7 +483,7 @@ class _GpuRecognizerFactory:
             from . import checkpoint as ckpt
             ckpt.restore(store, self.checkpoint)
         return Recognizer(store, decoder=self.decoder, beam_width=self.beam_width, allow_bf16=self.allow_bf16,
-                          detail=self.detail)
+                          detail=self.detail, lexicon=self.lexicon, lexicon_top=self.lexicon_top)
 
 
 class ReplicaError(RuntimeError):

@@ -149,6 +149,37 @@ int ocrk_ctc_align(const float* logits, const int* labels, const int* label_len,
                    float* path_logp, int* status, uint32_t* status_word, void* ws, size_t ws_bytes,
                    void* stream);
 
+/* Lexicon scoring: log p(word | logits) of every word of a list for every row (added within
+ * v7; no reference graph op: the reference's src/extract_fields and src/accuracy_measure
+ * match the recognised lines against known names on the host). Each score is the CTC
+ * forward sum of ocrk_ctc_loss (softmax inside, ctc_merge_repeated=True, blank = C-1) over
+ * the first L = clamp(seq_len[b], 0, T) frames, i.e. -loss, without a gradient or a stored
+ * lattice; the frames are normalised once per call, not once per word.
+ *   logits f32 [T, B, C] (C <= 256, T <= 4096)     seq_len i32 [B]
+ *   words  i32 [n_words][max_word_len] (dense, padded; max_word_len <= 255)
+ *   word_len i32 [n_words]; 1 <= n_words <= 2^20; 1 <= top_k <= 32
+ *   logp     f32 [B][n_words] or NULL: ln p(word | logits[:L, b]); -inf where the word
+ *            cannot be emitted in L frames (len + repeats > L, or L == 0)
+ *   top_idx  i32 [B][top_k], top_logp f32 [B][top_k]: the best valid, feasible words of
+ *            each row by (logp descending, word index ascending); past their number -1 and
+ *            -inf. top_logp[b][j] is logp[b][top_idx[b][j]] bit for bit.
+ *   log_norm f32 [B] or NULL: log-sum-exp of the row's finite scores, summed in a fixed
+ *            order (-inf if there are none): exp(top_logp - log_norm) is the posterior
+ *            within the lexicon. The whole call is reproducible bit for bit.
+ *   word_status i32 [n_words] or NULL: 0 ok, 2 word_len outside [0, max_word_len], 3 a
+ *            label outside [0, C-1). Such a word scores -inf on every row, is never
+ *            selected, its labels are never used as indices, and its
+ *            OCRK_STATUS_CTC_BAD_LENGTH / _BAD_LABEL bit is OR-ed into status_word (if given).
+ * UNLIKE ocrk_ctc_loss, an infeasible (word, row) pair is an ordinary result here -- a long
+ * word against a narrow crop: it sets no status bit and has no status code.
+ *   ws: >= ocrk_ctc_lexicon_workspace_size(T, B, C, n_words, max_word_len) bytes, 16-B
+ *       aligned (the normalised frames, the words' required frames, a score buffer). */
+size_t ocrk_ctc_lexicon_workspace_size(int T, int B, int C, int n_words, int max_word_len);
+int ocrk_ctc_lexicon_score(const float* logits, const int* seq_len, int T, int B, int C,
+                           const int* words, const int* word_len, int n_words, int max_word_len,
+                           int top_k, float* logp, int* top_idx, float* top_logp, float* log_norm,
+                           int* word_status, uint32_t* status_word, void* ws, size_t ws_bytes, void* stream);
+
 /* a10 -- validate._get_output (src/weinman/validate.py:81-92) =
  * tf.nn.ctc_greedy_decoder(logits, seq_len, merge_repeated) + sparse_to_dense(-1):
  *   out i64 [B, T] (labels then -1), out_len i32 [B], neg_sum_logits f32 [B] or NULL. */
