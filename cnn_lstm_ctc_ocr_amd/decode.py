@@ -10,6 +10,8 @@ places a decoded string's characters on the frames, for server.Recognition.
 Lexicon / ctc_lexicon_decoder have none either: they score a closed word list
 against the logits (what src/extract_fields and src/accuracy_measure do on the
 host with fuzzy matches of the decoded string), for server.LexiconRecognition.
+KeywordSet / ctc_keyword_spotter find keywords inside a line on the same logits
+(src/extract_fields/extractor.py's fuzzy regexes), for server.KeywordRecognition.
 Sparse outputs are returned dense, -1 padded (what sparse_tensor_to_dense(-1)
 gives the reference, validate.py:91-92), plus per-row lengths.
 """
@@ -20,6 +22,7 @@ from . import kernels as K
 from . import mjsynth
 
 MAX_WORD_LEN = 255                                          # the CTC kernels' label limit
+MAX_KEYWORD_LEN = 32                                        # ocrk_ctc_spot: 2 n - 1 states on the 64 lanes of a wave
 
 
 def _f32(logits):
@@ -145,6 +148,85 @@ def ctc_lexicon_decoder(inputs, sequence_length, lexicon, top_k=1):
     _logp, idx, logp, log_norm, _status = K.ctc_lexicon_score(
         _f32(inputs), sequence_length.to(torch.int32).contiguous(), lab, ln, top_k, need_scores=False)
     return idx, logp, log_norm
+
+
+class KeywordSet:
+    """An ordered list of keywords to find INSIDE recognised lines: strings over
+    mjsynth.out_charset, encoded once and kept as dense int32 labels,
+    alternatives and lengths per device. case_insensitive: the alternative of
+    an ASCII letter is its other case (other characters have none), and
+    duplicates are judged after case folding. ValueError for an empty list, an
+    empty string, a character outside the charset, a duplicate, or a keyword
+    over 32 characters (one lattice state per lane of a wave). Pickles as its
+    arguments (the device tensors are rebuilt where it lands)."""
+
+    def __init__(self, keywords, case_insensitive=False):
+        keywords = list(keywords)
+        if not keywords:
+            raise ValueError("KeywordSet: the keyword list is empty")
+        self.case_insensitive = bool(case_insensitive)
+        seen = set()
+        encoded = []
+        for i, w in enumerate(keywords):
+            if not isinstance(w, str):
+                raise ValueError(f"KeywordSet: entry {i} is {type(w).__name__}, not a string")
+            if not w:
+                raise ValueError(f"KeywordSet: entry {i} is the empty string")
+            if len(w) > MAX_KEYWORD_LEN:
+                raise ValueError(f"KeywordSet: entry {i} has {len(w)} characters (at most {MAX_KEYWORD_LEN})")
+            key = w.lower() if self.case_insensitive else w
+            if key in seen:
+                raise ValueError(f"KeywordSet: duplicate keyword {w!r} (entry {i})")
+            seen.add(key)
+            try:
+                encoded.append(mjsynth.encode(w))
+            except ValueError:
+                bad = next(ch for ch in w if ch not in mjsynth.out_charset)
+                raise ValueError(f"KeywordSet: {w!r} (entry {i}) has the character {bad!r} outside the "
+                                 "charset") from None
+        self.keywords = tuple(keywords)
+        self.lengths = np.array([len(e) for e in encoded], np.int32)
+        self.labels = np.zeros((len(encoded), int(self.lengths.max())), np.int32)
+        self.alternatives = np.full(self.labels.shape, -1, np.int32)
+        for i, (w, e) in enumerate(zip(keywords, encoded)):
+            self.labels[i, :len(e)] = e
+            if self.case_insensitive:
+                self.alternatives[i, :len(e)] = [mjsynth.out_charset.index(ch.swapcase())
+                                                 if ch.isascii() and ch.isalpha() else -1 for ch in w]
+        self._device = {}
+
+    def __len__(self):
+        return len(self.keywords)
+
+    def __reduce__(self):
+        return (KeywordSet, (list(self.keywords), self.case_insensitive))
+
+    def tensors(self, device):
+        """(labels i32 [n, max_len], alternatives i32 [n, max_len] or None when case-sensitive,
+        lengths i32 [n]) on `device`, uploaded once per device."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = (torch.from_numpy(self.labels).to(device),
+                                     torch.from_numpy(self.alternatives).to(device) if self.case_insensitive else None,
+                                     torch.from_numpy(self.lengths).to(device))
+        return t
+
+
+def ctc_keyword_spotter(inputs, sequence_length, keywords):
+    """Where each keyword of `keywords` (a KeywordSet) reads best inside each
+    row of inputs [T, B, C], on the first sequence_length[b] frames, free start
+    and free end (ocrk_ctc_spot; no reference graph op: what
+    src/extract_fields/extractor.py does on the host with fuzzy regexes over the
+    decoded string). Returns (score f32 [B, K]: ln of p(the best path spelling
+    the keyword on frames [first, end)) / p(the greedy path on those frames),
+    <= 0 and 0 when the greedy path spells it; span i32 [B, K, 2]: (first, end),
+    for frames_to_px). A keyword that does not fit the row has -inf and
+    (-1, -1). With case_insensitive keywords a run of one position may switch
+    between the two cases ("tT" reads as one "t"). Device tensors, no host sync."""
+    lab, alt, ln = keywords.tensors(inputs.device)
+    score, span, _status = K.ctc_spot(_f32(inputs), sequence_length.to(torch.int32).contiguous(), lab, alt, ln)
+    return score, span
 
 
 # Where a frame sits in the crop (src/weinman/model.py:134-163), in input-column

@@ -1019,6 +1019,38 @@ def ctc_lexicon_score(logits, seq_len, words, word_len, top_k=1, need_scores=Tru
     return logp, top_idx, top_logp, log_norm, word_status
 
 
+def ctc_spot(logits, seq_len, kw, kw_alt, kw_len):
+    """The best placement of every keyword inside every row, scored against the greedy path
+    (ocrk_ctc_spot).
+
+    logits f32 [T,B,C]; seq_len i32 [B]; kw i32 [K,Wmax] (dense, padded); kw_alt i32 [K,Wmax]
+    (an alternative label per position, -1 for none) or None; kw_len i32 [K] (1..32).
+    Returns (score f32 [B,K]: the natural-log likelihood ratio of the best path spelling the
+    keyword against the greedy path on the same frames, <= 0; span i32 [B,K,2]: (first, end)
+    frames of the hit; kw_status i32 [K]: 0 ok, 2 bad length, 3 bad label or alternative).
+    A keyword too long for a row scores -inf with span (-1, -1) there and sets no status bit."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_spot takes float32 logits")
+    if kw.dim() != 2 or kw_len.dim() != 1 or kw.shape[0] != kw_len.shape[0]:
+        raise ValueError("ctc_spot takes kw [K, Wmax] and kw_len [K]")
+    if kw_alt is not None and kw_alt.shape != kw.shape:
+        raise ValueError("ctc_spot takes kw_alt of kw's shape")
+    if any(t.dtype != torch.int32 for t in (kw, kw_len, seq_len) + (() if kw_alt is None else (kw_alt,))):
+        raise TypeError("ctc_spot takes int32 kw, kw_alt, kw_len and seq_len")
+    _chk(logits, seq_len, kw, kw_alt, kw_len)
+    T, B, C = logits.shape
+    n_kw, Wmax = kw.shape
+    dev = logits.device
+    nb = _lib.lib().ocrk_ctc_spot_workspace_size(T, B, C, n_kw, Wmax)
+    ws = _ws(nb, dev)
+    score = torch.empty(B, n_kw, dtype=torch.float32, device=dev)
+    span = torch.empty(B, n_kw, 2, dtype=torch.int32, device=dev)
+    kw_status = torch.empty(n_kw, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_spot", ptr(logits), ptr(seq_len), T, B, C, ptr(kw), ptr(kw_alt), ptr(kw_len), n_kw, Wmax,
+         ptr(score), ptr(span), ptr(kw_status), ptr(status_word(dev)), ptr(ws), nb, _stream(logits))
+    return score, span, kw_status
+
+
 def ctc_greedy_decode(logits, seq_len, merge_repeated=True):
     """Greedy decode. Returns (out i64 [B,T] -1 padded, out_len i32 [B], neg_sum f32 [B])."""
     if logits.dtype != torch.float32:

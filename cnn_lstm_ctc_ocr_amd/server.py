@@ -26,7 +26,7 @@ import math
 import queue
 import time
 from collections.abc import Sequence
-from typing import NamedTuple, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -96,6 +96,23 @@ def fill_batch(infos, batch, widths, bucket_size):
     return list(infos) + [("-1", "0")] * extra, batch, widths
 
 
+def _keyword_set(keywords, case_insensitive, who):
+    """keywords as a decode.KeywordSet (or None): a KeywordSet as it is, a sequence of strings encoded."""
+    if keywords is None or isinstance(keywords, decode.KeywordSet):
+        return keywords
+    if isinstance(keywords, str) or not isinstance(keywords, Sequence):
+        raise TypeError(f"{who}: keywords is a decode.KeywordSet or a sequence of strings, "
+                        f"not {type(keywords).__name__}")
+    return decode.KeywordSet(keywords, case_insensitive)
+
+
+def _keyword_threshold(value, who):
+    value = float(value)
+    if not value <= 0:                                       # a score is a log likelihood ratio <= 0 (NaN refused too)
+        raise ValueError(f"{who}: keyword_threshold is a log likelihood ratio, at most 0 (got {value})")
+    return value
+
+
 class Recognition(NamedTuple):
     """What Recognizer(detail=True) returns per crop (a plain tuple of built-in
     values: it crosses ReplicaPool's and a Manager's queues pickled)."""
@@ -115,6 +132,23 @@ class LexiconRecognition(NamedTuple):
     alternatives: Tuple[Tuple[str, float], ...]    # up to lexicon_top (word, log p), best first; [0] is text
     char_confidence: Tuple[float, ...]             # as Recognition, from the alignment of text
     char_px: Tuple[Tuple[float, float], ...]
+
+
+class KeywordHit(NamedTuple):
+    """One keyword found inside a crop (Recognizer(keywords=...)): built-in values only."""
+    keyword: str
+    score: float                                   # ln p(best path spelling it there) / p(greedy path there), <= 0
+    first_frame: int                               # the first frame of the first symbol
+    end_frame: int                                 # one past the last frame of the last symbol
+    x0: float                                      # decode.frames_to_px(first_frame, end_frame, width)
+    x1: float
+
+
+class KeywordRecognition(NamedTuple):
+    """What Recognizer(keywords=...) returns per crop (built-in values only, like Recognition)."""
+    text: str                                      # the string the same recogniser returns without keywords
+    detail: Optional[Recognition]                  # the Recognition with detail=True, else None
+    hits: Tuple[KeywordHit, ...]                   # score >= keyword_threshold; best first, then by keyword index
 
 
 class Recognizer:
@@ -137,10 +171,21 @@ class Recognizer:
     recognition. __call__ returns each crop's most probable lexicon word by
     log p(word | logits) (decode.ctc_lexicon_decoder; "" where no word fits the
     crop) and the unconstrained decoder is not launched; with detail=True a
-    LexiconRecognition with the best lexicon_top words."""
+    LexiconRecognition with the best lexicon_top words.
+
+    keywords (a decode.KeywordSet or a sequence of strings, then encoded with
+    case_insensitive): keyword spotting inside the line. __call__ returns a
+    KeywordRecognition per crop: the text (and the Recognition with
+    detail=True) exactly as without keywords, and a KeywordHit for every
+    keyword whose score (decode.ctc_keyword_spotter on the same forward's
+    logits: the log likelihood ratio of its best placement against the greedy
+    path, <= 0) reaches keyword_threshold (default ln 0.5), with its frames
+    and pixel columns. One more entry call per batch (two launches), none
+    without keywords. Not combined with lexicon."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
-                 graphs=False, detail=False, lexicon=None, lexicon_top=1):
+                 graphs=False, detail=False, lexicon=None, lexicon_top=1, keywords=None,
+                 keyword_threshold=math.log(0.5), case_insensitive=False):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -161,6 +206,10 @@ class Recognizer:
             raise ValueError("Recognizer: lexicon_top is 1..32")
         self.lexicon = lexicon
         self.lexicon_top = int(lexicon_top)
+        self.keywords = _keyword_set(keywords, case_insensitive, "Recognizer")
+        if self.keywords is not None and lexicon is not None:
+            raise ValueError("Recognizer: keywords and lexicon are two different questions; pass one of them")
+        self.keyword_threshold = _keyword_threshold(keyword_threshold, "Recognizer")
 
     def _graphed(self, batch, widths, decoded=True):
         """decoded=False: the forward alone (the lexicon path launches no unconstrained decoder)."""
@@ -224,7 +273,9 @@ class Recognizer:
         from two adjacent frames) keeps its text with confidence 0.0, zero
         character confidences and (0.0, 0.0) extents; the CTC bits such a row
         sets in the device status word are cleared here."""
-        logits, seq_len, out, out_len = self._decoded(batch, widths)
+        return self._recognitions(*self._decoded(batch, widths), widths)
+
+    def _recognitions(self, logits, seq_len, out, out_len, widths):
         with torch.no_grad():
             n_max = int(out_len.max().item()) if out_len.numel() else 0
             lab, ln = decode._masked_labels(out[:, :n_max], out_len)
@@ -313,7 +364,37 @@ class Recognizer:
                                           alts, cc, cp))
         return res
 
+    def keyword_recognitions(self, batch, widths):
+        """One KeywordRecognition per crop: the decode of labels() / recognitions(), and the spotting
+        launch on the same forward's logits (the replayed graph's, with graphs=True). A keyword that
+        does not fit a crop's frames has no place and is never a hit."""
+        logits, seq_len, out, out_len = self._decoded(batch, widths)
+        with torch.no_grad():
+            score, span = decode.ctc_keyword_spotter(logits, seq_len, self.keywords)
+        if self.detail:
+            details = self._recognitions(logits, seq_len, out, out_len, widths)
+            texts = [d.text for d in details]
+        else:
+            details = [None] * len(widths)
+            rows, lens = out.cpu().numpy(), out_len.cpu().tolist()       # labels then -1: the first out_len count
+            texts = [validate._get_string(row[:n]) for row, n in zip(rows, lens)]
+        score, span = score.cpu().numpy(), span.cpu().numpy()
+        # whole-array host work on the hits alone: by crop, then score descending, then keyword index
+        bs, ks = np.nonzero((score >= self.keyword_threshold) & (span[:, :, 0] >= 0))
+        order = np.lexsort((ks, -score[bs, ks], bs))
+        bs, ks = bs[order], ks[order]
+        first, end = span[bs, ks, 0], span[bs, ks, 1]
+        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        words = self.keywords.keywords
+        hits = [[] for _ in texts]
+        for b, k, s, f, e, a0, a1 in zip(bs.tolist(), ks.tolist(), score[bs, ks].tolist(), first.tolist(),
+                                         end.tolist(), np.atleast_1d(x0).tolist(), np.atleast_1d(x1).tolist()):
+            hits[b].append(KeywordHit(words[k], s, f, e, a0, a1))
+        return [KeywordRecognition(text, d, tuple(h)) for text, d, h in zip(texts, details, hits)]
+
     def __call__(self, batch, widths):
+        if self.keywords is not None:
+            return self.keyword_recognitions(batch, widths)
         if self.lexicon is not None:
             return self.lexicon_recognitions(batch, widths) if self.detail else self.lexicon_words(batch, widths)
         if self.detail:
@@ -458,22 +539,30 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
 
 
 def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
-                   detail=False, lexicon=None, lexicon_top=1):
+                   detail=False, lexicon=None, lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5),
+                   case_insensitive=False):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
-    reference initialisers with `seed`). Picklable (spawn); a lexicon travels
-    as its plain list of strings and is encoded in the replica."""
-    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top)
+    reference initialisers with `seed`). Picklable (spawn); a lexicon or a
+    keyword list travels as its plain list of strings and is encoded in the replica."""
+    return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top,
+                                 keywords, keyword_threshold, case_insensitive)
 
 
 class _GpuRecognizerFactory:
     def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False, lexicon=None,
-                 lexicon_top=1):
+                 lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5), case_insensitive=False):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
         self.allow_bf16, self.detail = allow_bf16, detail
         if lexicon is not None:                             # checked here, in the parent; pickled as strings
             lexicon = list(decode.Lexicon(lexicon).words if not isinstance(lexicon, decode.Lexicon) else lexicon.words)
         self.lexicon, self.lexicon_top = lexicon, lexicon_top
+        kws = _keyword_set(keywords, case_insensitive, "gpu_recognizer")     # checked here too; pickled as strings
+        if kws is not None and lexicon is not None:
+            raise ValueError("gpu_recognizer: keywords and lexicon are two different questions; pass one of them")
+        self.keywords = None if kws is None else list(kws.keywords)
+        self.case_insensitive = bool(case_insensitive) if kws is None else kws.case_insensitive
+        self.keyword_threshold = _keyword_threshold(keyword_threshold, "gpu_recognizer")
 
     def __call__(self, device):
         from .config import ModelConfig
@@ -483,7 +572,9 @@ class _GpuRecognizerFactory:
             from . import checkpoint as ckpt
             ckpt.restore(store, self.checkpoint)
         return Recognizer(store, decoder=self.decoder, beam_width=self.beam_width, allow_bf16=self.allow_bf16,
-                          detail=self.detail, lexicon=self.lexicon, lexicon_top=self.lexicon_top)
+                          detail=self.detail, lexicon=self.lexicon, lexicon_top=self.lexicon_top,
+                          keywords=self.keywords, keyword_threshold=self.keyword_threshold,
+                          case_insensitive=self.case_insensitive)
 
 
 class ReplicaError(RuntimeError):

@@ -180,6 +180,51 @@ int ocrk_ctc_lexicon_score(const float* logits, const int* seq_len, int T, int B
                            int top_k, float* logp, int* top_idx, float* top_logp, float* log_norm,
                            int* word_status, uint32_t* status_word, void* ws, size_t ws_bytes, void* stream);
 
+/* Keyword spotting: the best placement of every keyword of a list INSIDE every row, free start
+ * and free end, as a likelihood ratio against the greedy path, with the frames of the hit
+ * (added within v7; no reference graph op: the reference's src/extract_fields/extractor.py
+ * looks for its keywords in the decoded lines on the host, with fuzzy regexes).
+ * For row b, L = clamp(seq_len[b], 0, T) frames count and rel[t][c] = logits[t][b][c] -
+ * max_c logits[t][b][c], one float32 subtraction (<= 0, exactly 0 at the frame's argmax): the
+ * frame log-sum-exp cancels in a ratio of two paths over the same frames, so rel is already a
+ * natural-log likelihood ratio against the greedy path and no transcendental is taken.
+ * A keyword of n symbols (1 <= n <= 32) l_0..l_{n-1} in [0, C-1), each with an alternative
+ * a_i in [0, C-1) or -1 for none (case-insensitive matching), has S = 2 n - 1 states: even s
+ * is symbol s/2, odd s the blank (class C-1) between two symbols; there is no leading or
+ * trailing blank, the frames outside the hit belong to the filler. Emission e[t][s] =
+ * rel[t][l_i], or max(rel[t][l_i], rel[t][a_i]) when a_i >= 0; rel[t][C-1] for a blank state.
+ * V[t][s] = best + e[t][s], one float32 add, where best is taken among, in this order, a
+ * later candidate replacing the current one only if strictly greater: V[t-1][s]; V[t-1][s-1];
+ * V[t-1][s-2], only for even s >= 2 whose symbol sets {l_i, a_i} and {l_{i-1}, a_{i-1}} are
+ * disjoint; for s = 0 only, float32 0 (entry: the filler before the hit is the greedy path).
+ * Every state carries the frame at which its path entered state 0, taken from the chosen
+ * candidate (entry at frame t carries t); before frame 0 all V are -inf. After each frame
+ * (V[t][S-1], its start, t + 1) replaces the row's best only if strictly greater: among equal
+ * scores the earliest end, then the start the tie order produced. With alternatives a run of
+ * one position may switch between its two labels ("tT" counts as one "t").
+ *   logits f32 [T, B, C] (C <= 256, T <= 4096)     seq_len i32 [B]
+ *   kw     i32 [n_kw][max_kw_len] (dense, padded; 1 <= max_kw_len <= 255)
+ *   kw_alt i32 [n_kw][max_kw_len] or NULL (no keyword has alternatives)
+ *   kw_len i32 [n_kw]; 1 <= n_kw <= 2^20
+ *   score  f32 [B][n_kw]: ln(p(best path spelling the keyword on [first, end)) / p(greedy path
+ *          on those frames)), <= 0, and 0 when the frame-argmax path spells the keyword
+ *   span   i32 [B][n_kw][2]: (first, end) = the first frame of the first symbol, one past the
+ *          last frame of the last symbol; 8-B aligned
+ * A keyword needing more frames than L (n + the adjacent positions whose sets overlap) scores
+ * -inf with span (-1, -1) and sets no status bit: an ordinary result, as in the lexicon scorer.
+ *   kw_status i32 [n_kw] or NULL: 0 ok, 2 kw_len outside [1, min(32, max_kw_len)], 3 a label
+ *          outside [0, C-1) or an alternative outside {-1} and [0, C-1). Such a keyword scores
+ *          -inf with span (-1, -1) on every row, its labels are never used as indices, and its
+ *          OCRK_STATUS_CTC_BAD_LENGTH / _BAD_LABEL bit is OR-ed into status_word (if given).
+ * No floating-point atomics: the whole call is reproducible bit for bit.
+ *   ws: >= ocrk_ctc_spot_workspace_size(T, B, C, n_kw, max_kw_len) bytes, 16-B aligned (the
+ *       rel table and the keywords' required frames). */
+size_t ocrk_ctc_spot_workspace_size(int T, int B, int C, int n_kw, int max_kw_len);
+int ocrk_ctc_spot(const float* logits, const int* seq_len, int T, int B, int C, const int* kw,
+                  const int* kw_alt, const int* kw_len, int n_kw, int max_kw_len, float* score,
+                  int* span, int* kw_status, uint32_t* status_word, void* ws, size_t ws_bytes,
+                  void* stream);
+
 /* a10 -- validate._get_output (src/weinman/validate.py:81-92) =
  * tf.nn.ctc_greedy_decoder(logits, seq_len, merge_repeated) + sparse_to_dense(-1):
  *   out i64 [B, T] (labels then -1), out_len i32 [B], neg_sum_logits f32 [B] or NULL. */
