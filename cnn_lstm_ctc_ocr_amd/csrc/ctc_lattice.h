@@ -1,7 +1,8 @@
 // The extended-label lattice helpers shared by the CTC loss / alignment
 // (ctc.hip) and the lexicon scorer (ctc_lexicon.hip): base-2 log-sum-exps and
 // the state shifts of a lattice held in the registers of one wave (lane j
-// holds states j, j + 64, ...: R registers).
+// holds states j, j + 64, ...: R registers); and the rel table of the keyword
+// spotter (ctc_spot.hip) and the field reader (ctc_field.hip).
 #pragma once
 #include <cfloat>
 
@@ -60,4 +61,31 @@ __device__ __forceinline__ float wave_shr1(float v) {
 __device__ __forceinline__ float wave_shl1(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, -INFINITY),
                                                                  __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, false));
+}
+
+// The frame part of the spotter's and the field reader's prep launches: one wave
+// of a THREADS-wide workgroup per frame (b, t) writes rel = logit - max_c logit,
+// a single float32 subtraction, into tab[b][t][c]. Frames at or past the row's
+// length are neither read nor written.
+template <int THREADS>
+__device__ __forceinline__ void ctc_rel_frame(const float* __restrict__ logits, const int* __restrict__ seq_len, int T,
+                                              int B, int C, float* __restrict__ tab) {
+    constexpr int NQ = CTC_MAX_C / 64;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t f = (int64_t)blockIdx.x * (THREADS / 64) + wave;
+    if (f >= (int64_t)B * T) return;
+    const int b = (int)(f / T), t = (int)(f % T);
+    if (t >= min(max(seq_len[b], 0), T)) return;           // frames past the sequence are never read
+    const float* row = logits + ((size_t)t * B + b) * C;
+    float v[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = lane + 64 * q < C ? row[lane + 64 * q] : -INFINITY;
+    float m = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) m = fmaxf(m, v[q]);
+    m = wave_max_dpp(m);
+    float* out = tab + ((size_t)b * T + t) * C;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+        if (lane + 64 * q < C) out[lane + 64 * q] = v[q] - m;
 }

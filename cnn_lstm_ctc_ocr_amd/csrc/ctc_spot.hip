@@ -59,25 +59,7 @@ spot_prep_kernel(const float* __restrict__ logits, const int* __restrict__ seq_l
                  int max_kw_len, float* __restrict__ tab, int* __restrict__ kinfo, int* __restrict__ kw_status,
                  unsigned* __restrict__ status_word, int frame_blocks) {
     if ((int)blockIdx.x < frame_blocks) {
-        // one wave per frame (b, t): rel = logit - max, a single float32 subtraction
-        constexpr int NQ = CTC_MAX_C / 64;
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        const int64_t f = (int64_t)blockIdx.x * (SPOT_PREP_THREADS / 64) + wave;
-        if (f >= (int64_t)B * T) return;
-        const int b = (int)(f / T), t = (int)(f % T);
-        if (t >= min(max(seq_len[b], 0), T)) return;       // frames past the sequence are never read
-        const float* row = logits + ((size_t)t * B + b) * C;
-        float v[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v[q] = lane + 64 * q < C ? row[lane + 64 * q] : -INFINITY;
-        float m = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) m = fmaxf(m, v[q]);
-        m = wave_max_dpp(m);
-        float* out = tab + ((size_t)b * T + t) * C;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-            if (lane + 64 * q < C) out[lane + 64 * q] = v[q] - m;
+        ctc_rel_frame<SPOT_PREP_THREADS>(logits, seq_len, T, B, C, tab);
         return;
     }
     // one thread per keyword, with no row in sight. A bad length never indexes the label rows; a bad label

@@ -12,6 +12,9 @@ against the logits (what src/extract_fields and src/accuracy_measure do on the
 host with fuzzy matches of the decoded string), for server.LexiconRecognition.
 KeywordSet / ctc_keyword_spotter find keywords inside a line on the same logits
 (src/extract_fields/extractor.py's fuzzy regexes), for server.KeywordRecognition.
+FieldSet / ctc_field_reader read the best string matching a small character-class
+pattern out of a line on the same logits (extractor.py's amount, GST and receipt
+number regexes over the 1-best string), for server.FieldRecognition.
 Sparse outputs are returned dense, -1 padded (what sparse_tensor_to_dense(-1)
 gives the reference, validate.py:91-92), plus per-row lengths.
 """
@@ -23,6 +26,9 @@ from . import mjsynth
 
 MAX_WORD_LEN = 255                                          # the CTC kernels' label limit
 MAX_KEYWORD_LEN = 32                                        # ocrk_ctc_spot: 2 n - 1 states on the 64 lanes of a wave
+MAX_FIELD_LEN = 16                                          # ocrk_ctc_field: positions of a pattern,
+MAX_FIELD_CLASS = 16                                        # characters of a class (one per lane of a 16-lane row),
+MAX_FIELD_OPTIONAL = 3                                      # and optional positions in a row
 
 
 def _f32(logits):
@@ -227,6 +233,198 @@ def ctc_keyword_spotter(inputs, sequence_length, keywords):
     lab, alt, ln = keywords.tensors(inputs.device)
     score, span, _status = K.ctc_spot(_f32(inputs), sequence_length.to(torch.int32).contiguous(), lab, alt, ln)
     return score, span
+
+
+_FIELD_SPECIAL = "\\[]{}?.*+()|^$"                          # literals only when escaped
+_FIELD_UNSUPPORTED = ".*+()|^$"                             # what a regular expression has and a field pattern lacks
+
+
+def _field_char(name, pattern, ch):
+    if ch not in mjsynth.out_charset:
+        raise ValueError(f"FieldSet: {name!r}: {pattern!r} has the character {ch!r} outside the charset")
+    return ch
+
+
+def _field_escape(name, pattern, i):
+    """The characters of the escape whose backslash is pattern[i], and the index after it."""
+    if i + 1 >= len(pattern):
+        raise ValueError(f"FieldSet: {name!r}: {pattern!r} ends in a backslash")
+    ch = pattern[i + 1]
+    if ch == "d":
+        return "0123456789", i + 2
+    if ch in _FIELD_SPECIAL or ch == "-":                    # \- for a hyphen inside a class that is no range
+        return _field_char(name, pattern, ch), i + 2
+    raise ValueError(f"FieldSet: {name!r}: unsupported escape \\{ch} in {pattern!r}")
+
+
+def _field_class(name, pattern, i):
+    """The characters of the class whose '[' is pattern[i], and the index after its ']'."""
+    chars = []
+    i += 1
+    if i < len(pattern) and pattern[i] == "^":
+        raise ValueError(f"FieldSet: {name!r}: unsupported negated class in {pattern!r}")
+    while True:
+        if i >= len(pattern):
+            raise ValueError(f"FieldSet: {name!r}: unterminated class in {pattern!r}")
+        ch = pattern[i]
+        if ch == "]":
+            break
+        if ch == "\\":
+            item, i = _field_escape(name, pattern, i)
+        elif ch in _FIELD_SPECIAL:
+            raise ValueError(f"FieldSet: {name!r}: {ch!r} inside a class of {pattern!r} is written \\{ch}")
+        else:
+            item, i = _field_char(name, pattern, ch), i + 1
+        if len(item) == 1 and i + 1 < len(pattern) and pattern[i] == "-" and pattern[i + 1] != "]":
+            if pattern[i + 1] == "\\":
+                hi, i = _field_escape(name, pattern, i + 1)
+            elif pattern[i + 1] in _FIELD_SPECIAL:
+                raise ValueError(f"FieldSet: {name!r}: {pattern[i + 1]!r} inside a class of {pattern!r} is "
+                                 f"written \\{pattern[i + 1]}")
+            else:
+                hi, i = _field_char(name, pattern, pattern[i + 1]), i + 2
+            if len(hi) != 1 or ord(hi) < ord(item):
+                raise ValueError(f"FieldSet: {name!r}: bad range {item}-{hi} in {pattern!r}")
+            item = "".join(_field_char(name, pattern, chr(c)) for c in range(ord(item), ord(hi) + 1))
+        chars.extend(item)
+    if not chars:
+        raise ValueError(f"FieldSet: {name!r}: empty class in {pattern!r}")
+    return "".join(chars), i + 1
+
+
+def _field_quantifier(name, pattern, i):
+    """(m, n, index after) of the quantifier at pattern[i]; (1, 1, i) where there is none."""
+    if i < len(pattern) and pattern[i] == "?":
+        return 0, 1, i + 1
+    if i >= len(pattern) or pattern[i] != "{":
+        return 1, 1, i
+    j = pattern.find("}", i)
+    body = pattern[i + 1:j] if j >= 0 else ""
+    parts = body.split(",")
+    if j < 0 or len(parts) > 2 or not all(p.isascii() and p.isdigit() for p in parts):
+        raise ValueError(f"FieldSet: {name!r}: bad quantifier in {pattern!r} ({{m}} or {{m,n}})")
+    m, n = int(parts[0]), int(parts[-1])
+    if not m <= n or n - m > MAX_FIELD_OPTIONAL:
+        raise ValueError(f"FieldSet: {name!r}: quantifier {{{body}}} in {pattern!r} needs m <= n <= m + "
+                         f"{MAX_FIELD_OPTIONAL}")
+    return m, n, j + 1
+
+
+def compile_field(name, pattern):
+    """A field pattern as (classes, optional): per position the sorted labels of its class and
+    whether the position may be absent. The grammar is deliberately small: a literal character of
+    mjsynth.out_charset (the characters \\ [ ] { } ? . * + ( ) | ^ $ only when escaped with a
+    backslash), \\d, a class [...] of characters, ranges and escapes without negation, each followed
+    by nothing, ?, {m} or {m,n} with n - m <= 3 (m mandatory copies, then n - m optional ones).
+    ValueError for anything else, naming the pattern."""
+    if not isinstance(pattern, str):
+        raise ValueError(f"FieldSet: {name!r} is {type(pattern).__name__}, not a string")
+    classes, optional = [], []
+    i = 0
+    while i < len(pattern):
+        ch = pattern[i]
+        if ch == "\\":
+            chars, i = _field_escape(name, pattern, i)
+        elif ch == "[":
+            chars, i = _field_class(name, pattern, i)
+        elif ch in _FIELD_UNSUPPORTED:
+            raise ValueError(f"FieldSet: {name!r}: unsupported {ch!r} in {pattern!r} (escape it for the character)")
+        elif ch in _FIELD_SPECIAL:
+            raise ValueError(f"FieldSet: {name!r}: stray {ch!r} in {pattern!r} (escape it for the character)")
+        else:
+            chars, i = _field_char(name, pattern, ch), i + 1
+        labels = sorted({mjsynth.out_charset.index(c) for c in chars})
+        if len(labels) > MAX_FIELD_CLASS:
+            raise ValueError(f"FieldSet: {name!r}: a class of {pattern!r} has {len(labels)} characters "
+                             f"(at most {MAX_FIELD_CLASS})")
+        m, n, i = _field_quantifier(name, pattern, i)
+        classes += [labels] * n
+        optional += [False] * m + [True] * (n - m)
+    if not 1 <= len(classes) <= MAX_FIELD_LEN:
+        raise ValueError(f"FieldSet: {name!r}: {pattern!r} has {len(classes)} positions (1..{MAX_FIELD_LEN})")
+    if optional[0]:
+        raise ValueError(f"FieldSet: {name!r}: {pattern!r} begins with an optional position")
+    run = 0
+    for o in optional:
+        run = run + 1 if o else 0
+        if run > MAX_FIELD_OPTIONAL:
+            raise ValueError(f"FieldSet: {name!r}: {pattern!r} has more than {MAX_FIELD_OPTIONAL} optional "
+                             "positions in a row")
+    return classes, optional
+
+
+class FieldSet:
+    """Named field patterns to read out of recognised lines (amounts, GST, receipt
+    numbers: what src/extract_fields/extractor.py reads with regular expressions
+    over the decoded string): a mapping name -> pattern in compile_field's
+    grammar, compiled once and kept as dense int32 classes, optional flags and
+    lengths per device. ValueError for an empty mapping or a pattern outside the
+    grammar or its limits (16 positions, 16 characters per class, a mandatory
+    first position, at most 3 optional positions in a row). Pickles as its
+    mapping (the device tensors are rebuilt where it lands)."""
+
+    def __init__(self, patterns):
+        if not hasattr(patterns, "items"):
+            raise TypeError(f"FieldSet: patterns is a mapping name -> pattern, not {type(patterns).__name__}")
+        patterns = dict(patterns)
+        if not patterns:
+            raise ValueError("FieldSet: the pattern mapping is empty")
+        for name in patterns:
+            if not isinstance(name, str):
+                raise ValueError(f"FieldSet: the name {name!r} is {type(name).__name__}, not a string")
+        self.patterns = patterns
+        self.names = tuple(patterns)
+        self.compiled = tuple(compile_field(name, pat) for name, pat in patterns.items())
+        self.lengths = np.array([len(c) for c, _ in self.compiled], np.int32)
+        width = int(self.lengths.max())
+        self.classes = np.full((len(self.compiled), width, MAX_FIELD_CLASS), -1, np.int32)
+        self.optional = np.zeros((len(self.compiled), width), np.int32)
+        for p, (cls, opt) in enumerate(self.compiled):
+            for i, labels in enumerate(cls):
+                self.classes[p, i, :len(labels)] = labels
+            self.optional[p, :len(opt)] = opt
+        self._device = {}
+
+    def __len__(self):
+        return len(self.names)
+
+    def __reduce__(self):
+        return (FieldSet, (dict(self.patterns),))
+
+    def tensors(self, device):
+        """(classes i32 [n, max_len, 16], optional i32 [n, max_len], lengths i32 [n]) on `device`,
+        uploaded once per device."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = (torch.from_numpy(self.classes).to(device),
+                                     torch.from_numpy(self.optional).to(device),
+                                     torch.from_numpy(self.lengths).to(device))
+        return t
+
+    def strings(self, text):
+        """The string of each row of `text` (int labels [..., max_len], -1 = absent), as a nested list."""
+        text = np.asarray(text)
+        flat = ["".join(mjsynth.out_charset[l] for l in row if l >= 0) for row in text.reshape(-1, text.shape[-1])]
+        return np.array(flat, dtype=object).reshape(text.shape[:-1]).tolist()
+
+
+def ctc_field_reader(inputs, sequence_length, fields):
+    """The best-scoring string matching each pattern of `fields` (a FieldSet)
+    inside each row of inputs [T, B, C], on the first sequence_length[b] frames,
+    placed anywhere (ocrk_ctc_field; no reference graph op: what
+    src/extract_fields/extractor.py does on the host with regular expressions
+    over the 1-best string, where one digit misread as its runner-up silently
+    changes an amount). Returns (score f32 [B, P]: ln of p(the best path
+    spelling a matching string on frames [first, end)) / p(the greedy path on
+    those frames), <= 0 and 0 when the greedy path spells one; span i32
+    [B, P, 2]: (first, end), for frames_to_px; text i32 [B, P, max_len]: the
+    label chosen at each position, -1 for an absent one: FieldSet.strings turns
+    it into strings). A pattern that fits the row nowhere has -inf, (-1, -1) and
+    -1s. Device tensors, no host sync."""
+    cls, opt, ln = fields.tensors(inputs.device)
+    score, span, text, _status = K.ctc_field(_f32(inputs), sequence_length.to(torch.int32).contiguous(), cls, opt, ln)
+    return score, span, text
 
 
 # Where a frame sits in the crop (src/weinman/model.py:134-163), in input-column

@@ -1051,6 +1051,42 @@ def ctc_spot(logits, seq_len, kw, kw_alt, kw_len):
     return score, span, kw_status
 
 
+def ctc_field(logits, seq_len, pat_cls, pat_opt, pat_len):
+    """The best-scoring string matching every character-class pattern inside every row, scored
+    against the greedy path (ocrk_ctc_field).
+
+    logits f32 [T,B,C]; seq_len i32 [B]; pat_cls i32 [P,Wmax,16] (per position 1..16 labels
+    strictly ascending, -1 padded); pat_opt i32 [P,Wmax] (non-zero: the position may be absent);
+    pat_len i32 [P] (1..16).
+    Returns (score f32 [B,P]: the natural-log likelihood ratio of the best path spelling a
+    matching string against the greedy path on the same frames, <= 0; span i32 [B,P,2]: (first,
+    end) frames of the hit; text i32 [B,P,Wmax]: the label chosen per position, -1 for an absent
+    or unused one; pat_status i32 [P]: 0 ok, 2 bad length or structure, 3 bad class).
+    A pattern no string of which fits a row scores -inf with span (-1, -1) there and sets no
+    status bit."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_field takes float32 logits")
+    if (pat_cls.dim() != 3 or pat_cls.shape[2] != 16 or pat_len.dim() != 1 or pat_cls.shape[0] != pat_len.shape[0]):
+        raise ValueError("ctc_field takes pat_cls [P, Wmax, 16] and pat_len [P]")
+    if pat_opt.shape != pat_cls.shape[:2]:
+        raise ValueError("ctc_field takes pat_opt [P, Wmax] beside pat_cls [P, Wmax, 16]")
+    if any(t.dtype != torch.int32 for t in (pat_cls, pat_opt, pat_len, seq_len)):
+        raise TypeError("ctc_field takes int32 pat_cls, pat_opt, pat_len and seq_len")
+    _chk(logits, seq_len, pat_cls, pat_opt, pat_len)
+    T, B, C = logits.shape
+    n_pat, Wmax = pat_opt.shape
+    dev = logits.device
+    nb = _lib.lib().ocrk_ctc_field_workspace_size(T, B, C, n_pat, Wmax)
+    ws = _ws(nb, dev)
+    score = torch.empty(B, n_pat, dtype=torch.float32, device=dev)
+    span = torch.empty(B, n_pat, 2, dtype=torch.int32, device=dev)
+    text = torch.empty(B, n_pat, Wmax, dtype=torch.int32, device=dev)
+    pat_status = torch.empty(n_pat, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_field", ptr(logits), ptr(seq_len), T, B, C, ptr(pat_cls), ptr(pat_opt), ptr(pat_len), n_pat, Wmax,
+         ptr(score), ptr(span), ptr(text), ptr(pat_status), ptr(status_word(dev)), ptr(ws), nb, _stream(logits))
+    return score, span, text, pat_status
+
+
 def ctc_greedy_decode(logits, seq_len, merge_repeated=True):
     """Greedy decode. Returns (out i64 [B,T] -1 padded, out_len i32 [B], neg_sum f32 [B])."""
     if logits.dtype != torch.float32:

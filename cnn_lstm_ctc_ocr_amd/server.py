@@ -25,7 +25,7 @@ service is built with decoder="beam" (BASELINE config C5, beam 16).
 import math
 import queue
 import time
-from collections.abc import Sequence
+from collections.abc import Mapping, Sequence
 from typing import NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -113,6 +113,23 @@ def _keyword_threshold(value, who):
     return value
 
 
+def _field_set(fields, who):
+    """fields as a decode.FieldSet (or None): a FieldSet as it is, a mapping name -> pattern compiled."""
+    if fields is None or isinstance(fields, decode.FieldSet):
+        return fields
+    if not isinstance(fields, Mapping):
+        raise TypeError(f"{who}: fields is a decode.FieldSet or a mapping name -> pattern, "
+                        f"not {type(fields).__name__}")
+    return decode.FieldSet(fields)
+
+
+def _field_threshold(value, who):
+    value = float(value)
+    if not value <= 0:
+        raise ValueError(f"{who}: field_threshold is a log likelihood ratio, at most 0 (got {value})")
+    return value
+
+
 class Recognition(NamedTuple):
     """What Recognizer(detail=True) returns per crop (a plain tuple of built-in
     values: it crosses ReplicaPool's and a Manager's queues pickled)."""
@@ -151,6 +168,25 @@ class KeywordRecognition(NamedTuple):
     hits: Tuple[KeywordHit, ...]                   # score >= keyword_threshold; best first, then by keyword index
 
 
+class FieldHit(NamedTuple):
+    """One field read out of a crop (Recognizer(fields=...)): built-in values only."""
+    name: str
+    text: str                                      # the best-scoring string matching the field's pattern
+    score: float                                   # ln p(best path spelling it there) / p(greedy path there), <= 0
+    first_frame: int                               # the first frame of the first symbol
+    end_frame: int                                 # one past the last frame of the last symbol
+    x0: float                                      # decode.frames_to_px(first_frame, end_frame, width)
+    x1: float
+
+
+class FieldRecognition(NamedTuple):
+    """What Recognizer(fields=...) returns per crop (built-in values only, like Recognition)."""
+    text: str                                      # the string the same recogniser returns without fields
+    detail: Optional[Recognition]                  # the Recognition with detail=True, else None
+    hits: Tuple[KeywordHit, ...]                   # as KeywordRecognition.hits when keywords are given too, else ()
+    fields: Tuple[FieldHit, ...]                   # score >= field_threshold; best first, then by pattern order
+
+
 class Recognizer:
     """The per-batch model step of LocalServer.run (server.py:80-89, 132-138):
     uint8 [bs, 32, W, 1] + widths -> one string per crop. Holds the variables
@@ -181,11 +217,21 @@ class Recognizer:
     logits: the log likelihood ratio of its best placement against the greedy
     path, <= 0) reaches keyword_threshold (default ln 0.5), with its frames
     and pixel columns. One more entry call per batch (two launches), none
-    without keywords. Not combined with lexicon."""
+    without keywords. Not combined with lexicon.
+
+    fields (a decode.FieldSet or a mapping name -> pattern): field reading
+    inside the line. __call__ returns a FieldRecognition per crop: text and
+    detail exactly as without fields, hits as with keywords alone (() without
+    keywords), and a FieldHit for every pattern whose best matching string
+    (decode.ctc_field_reader on the same forward's logits) scores at least
+    field_threshold (default ln 0.5), with its frames and pixel columns. One
+    more entry call per batch (two launches), none without fields. Not
+    combined with lexicon."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
                  graphs=False, detail=False, lexicon=None, lexicon_top=1, keywords=None,
-                 keyword_threshold=math.log(0.5), case_insensitive=False):
+                 keyword_threshold=math.log(0.5), case_insensitive=False, fields=None,
+                 field_threshold=math.log(0.5)):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -210,6 +256,10 @@ class Recognizer:
         if self.keywords is not None and lexicon is not None:
             raise ValueError("Recognizer: keywords and lexicon are two different questions; pass one of them")
         self.keyword_threshold = _keyword_threshold(keyword_threshold, "Recognizer")
+        self.fields = _field_set(fields, "Recognizer")
+        if self.fields is not None and lexicon is not None:
+            raise ValueError("Recognizer: fields and lexicon are two different questions; pass one of them")
+        self.field_threshold = _field_threshold(field_threshold, "Recognizer")
 
     def _graphed(self, batch, widths, decoded=True):
         """decoded=False: the forward alone (the lexicon path launches no unconstrained decoder)."""
@@ -368,16 +418,20 @@ class Recognizer:
         """One KeywordRecognition per crop: the decode of labels() / recognitions(), and the spotting
         launch on the same forward's logits (the replayed graph's, with graphs=True). A keyword that
         does not fit a crop's frames has no place and is never a hit."""
-        logits, seq_len, out, out_len = self._decoded(batch, widths)
-        with torch.no_grad():
-            score, span = decode.ctc_keyword_spotter(logits, seq_len, self.keywords)
+        return self._keyword_recognitions(*self._decoded(batch, widths), widths)
+
+    def _texts(self, logits, seq_len, out, out_len, widths):
+        """(texts, details) of a decoded batch: the Recognitions with detail=True, else None per crop."""
         if self.detail:
             details = self._recognitions(logits, seq_len, out, out_len, widths)
-            texts = [d.text for d in details]
-        else:
-            details = [None] * len(widths)
-            rows, lens = out.cpu().numpy(), out_len.cpu().tolist()       # labels then -1: the first out_len count
-            texts = [validate._get_string(row[:n]) for row, n in zip(rows, lens)]
+            return [d.text for d in details], details
+        rows, lens = out.cpu().numpy(), out_len.cpu().tolist()           # labels then -1: the first out_len count
+        return [validate._get_string(row[:n]) for row, n in zip(rows, lens)], [None] * len(widths)
+
+    def _keyword_recognitions(self, logits, seq_len, out, out_len, widths):
+        with torch.no_grad():
+            score, span = decode.ctc_keyword_spotter(logits, seq_len, self.keywords)
+        texts, details = self._texts(logits, seq_len, out, out_len, widths)
         score, span = score.cpu().numpy(), span.cpu().numpy()
         # whole-array host work on the hits alone: by crop, then score descending, then keyword index
         bs, ks = np.nonzero((score >= self.keyword_threshold) & (span[:, :, 0] >= 0))
@@ -392,7 +446,36 @@ class Recognizer:
             hits[b].append(KeywordHit(words[k], s, f, e, a0, a1))
         return [KeywordRecognition(text, d, tuple(h)) for text, d, h in zip(texts, details, hits)]
 
+    def field_recognitions(self, batch, widths):
+        """One FieldRecognition per crop: what keyword_recognitions() (with keywords) or labels() /
+        recognitions() give, and the field-reading launch on the same forward's logits (the replayed
+        graph's, with graphs=True). A pattern that fits a crop's frames nowhere is never a hit."""
+        decoded = self._decoded(batch, widths)
+        logits, seq_len = decoded[0], decoded[1]
+        with torch.no_grad():
+            score, span, text = decode.ctc_field_reader(logits, seq_len, self.fields)
+        if self.keywords is not None:
+            base = [(r.text, r.detail, r.hits) for r in self._keyword_recognitions(*decoded, widths)]
+        else:
+            base = [(t, d, ()) for t, d in zip(*self._texts(*decoded, widths))]
+        score, span, text = score.cpu().numpy(), span.cpu().numpy(), text.cpu().numpy()
+        # whole-array host work on the hits alone: by crop, then score descending, then pattern order
+        bs, ps = np.nonzero((score >= self.field_threshold) & (span[:, :, 0] >= 0))
+        order = np.lexsort((ps, -score[bs, ps], bs))
+        bs, ps = bs[order], ps[order]
+        first, end = span[bs, ps, 0], span[bs, ps, 1]
+        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        strings = self.fields.strings(text[bs, ps]) if len(bs) else []
+        names = self.fields.names
+        found = [[] for _ in base]
+        for b, p, w, s, f, e, a0, a1 in zip(bs.tolist(), ps.tolist(), strings, score[bs, ps].tolist(), first.tolist(),
+                                            end.tolist(), np.atleast_1d(x0).tolist(), np.atleast_1d(x1).tolist()):
+            found[b].append(FieldHit(names[p], w, s, f, e, a0, a1))
+        return [FieldRecognition(t, d, h, tuple(f)) for (t, d, h), f in zip(base, found)]
+
     def __call__(self, batch, widths):
+        if self.fields is not None:
+            return self.field_recognitions(batch, widths)
         if self.keywords is not None:
             return self.keyword_recognitions(batch, widths)
         if self.lexicon is not None:
@@ -540,18 +623,20 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
 
 def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
                    detail=False, lexicon=None, lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5),
-                   case_insensitive=False):
+                   case_insensitive=False, fields=None, field_threshold=math.log(0.5)):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
     reference initialisers with `seed`). Picklable (spawn); a lexicon or a
-    keyword list travels as its plain list of strings and is encoded in the replica."""
+    keyword list travels as its plain list of strings, field patterns as their plain
+    mapping, and they are encoded in the replica."""
     return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top,
-                                 keywords, keyword_threshold, case_insensitive)
+                                 keywords, keyword_threshold, case_insensitive, fields, field_threshold)
 
 
 class _GpuRecognizerFactory:
     def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False, lexicon=None,
-                 lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5), case_insensitive=False):
+                 lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5), case_insensitive=False,
+                 fields=None, field_threshold=math.log(0.5)):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
         self.allow_bf16, self.detail = allow_bf16, detail
         if lexicon is not None:                             # checked here, in the parent; pickled as strings
@@ -563,6 +648,11 @@ class _GpuRecognizerFactory:
         self.keywords = None if kws is None else list(kws.keywords)
         self.case_insensitive = bool(case_insensitive) if kws is None else kws.case_insensitive
         self.keyword_threshold = _keyword_threshold(keyword_threshold, "gpu_recognizer")
+        fset = _field_set(fields, "gpu_recognizer")                          # and the patterns; pickled as a mapping
+        if fset is not None and lexicon is not None:
+            raise ValueError("gpu_recognizer: fields and lexicon are two different questions; pass one of them")
+        self.fields = None if fset is None else dict(fset.patterns)
+        self.field_threshold = _field_threshold(field_threshold, "gpu_recognizer")
 
     def __call__(self, device):
         from .config import ModelConfig
@@ -574,7 +664,8 @@ class _GpuRecognizerFactory:
         return Recognizer(store, decoder=self.decoder, beam_width=self.beam_width, allow_bf16=self.allow_bf16,
                           detail=self.detail, lexicon=self.lexicon, lexicon_top=self.lexicon_top,
                           keywords=self.keywords, keyword_threshold=self.keyword_threshold,
-                          case_insensitive=self.case_insensitive)
+                          case_insensitive=self.case_insensitive, fields=self.fields,
+                          field_threshold=self.field_threshold)
 
 
 class ReplicaError(RuntimeError):

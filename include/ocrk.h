@@ -225,6 +225,64 @@ int ocrk_ctc_spot(const float* logits, const int* seq_len, int T, int B, int C, 
                   int* span, int* kw_status, uint32_t* status_word, void* ws, size_t ws_bytes,
                   void* stream);
 
+/* Field reading: the best-scoring string that matches a small character-class pattern, placed
+ * anywhere inside a row, as a likelihood ratio against the greedy path, with the frames of the
+ * hit and the label chosen at each position (added within v7; no reference graph op: the
+ * reference's src/extract_fields/extractor.py reads amounts, GST and receipt numbers out of the
+ * decoded lines on the host, with regular expressions over the 1-best string).
+ * A pattern is a sequence of n positions, 1 <= n <= 16. Position i has a class cls[i] of 1..16
+ * distinct labels in [0, C-1), strictly ascending, never the blank C-1, and a flag opt[i]: the
+ * position may be absent. Position 0 is mandatory, at most 3 consecutive positions are
+ * optional, trailing optional positions are allowed. With k[i] the number of consecutive
+ * optional positions immediately before i, the predecessors of position i are the positions
+ * i-1, i-2, ..., i-1-k[i] that are >= 0.
+ * For row b, L = clamp(seq_len[b], 0, T) and rel[t][c] = logits[t][b][c] - max_c logits[t][b][c]
+ * are ocrk_ctc_spot's. The lattice has per position i the state (i, blank), the blank after
+ * position i, and the states (i, j), j < |cls[i]|: position i is emitting label cls[i][j]. Every
+ * state carries V (float32, -inf before frame 0), the frame at which its path entered position
+ * 0, and the label chosen at each position so far (absent = -1). Per frame t, a later candidate
+ * replacing the current one only if strictly greater:
+ *   V[t][(i, blank)] = best + rel[t][C-1], best among, in this order: (i, blank); (i, 0),
+ *     (i, 1), ...; what the state carries comes from the chosen candidate.
+ *   V[t][(i, j)] = best + rel[t][l], l = cls[i][j], one float32 add, best among, in this order:
+ *     (i, j) itself; for each predecessor position q, nearest first: (q, blank), then (q, 0),
+ *     (q, 1), ... skipping the state whose label equals l (the same label twice needs the
+ *     blank); for i = 0 only, float32 0 with start t (the free start: the filler before the hit
+ *     is the greedy path). The state then records l at position i.
+ *   After each frame the end positions are visited: n-1, then back through the trailing
+ *     optional positions to the first mandatory one, nearest to n-1 first, j ascending within
+ *     each. A candidate (V, start, t + 1, labels) replaces the row's best if V is strictly
+ *     greater, or if V equals the best's finite score and has the same start (the hit extends:
+ *     "112.5" becomes "112.50"). Among equal scores this keeps the first-ending hit's start
+ *     and from that start the longest extension.
+ * The score is <= 0 and exactly 0 when the frame-argmax path spells a matching string on some
+ * frames; no transcendental is taken.
+ *   logits  f32 [T, B, C] (C <= 256, T <= 4096)     seq_len i32 [B]
+ *   pat_cls i32 [n_pat][max_pat_len][16] (-1 padded; 1 <= max_pat_len <= 255)
+ *   pat_opt i32 [n_pat][max_pat_len] (non-zero: optional)
+ *   pat_len i32 [n_pat]; 1 <= n_pat <= 2^20
+ *   score   f32 [B][n_pat]
+ *   span    i32 [B][n_pat][2]: (first, end) = the first frame of the first symbol, one past the
+ *           last frame of the last symbol; 8-B aligned
+ *   text    i32 [B][n_pat][max_pat_len]: the chosen label per position, -1 for an absent or
+ *           unused position
+ * A pattern with no path in L frames scores -inf with span (-1, -1) and labels -1 and sets no
+ * status bit: an ordinary result, as in the spotter and the lexicon scorer.
+ *   pat_status i32 [n_pat] or NULL: 0 ok, 2 pat_len outside [1, min(16, max_pat_len)], an
+ *           optional position 0 or more than 3 consecutive optional positions, 3 a class that
+ *           is empty, has a label outside [0, C-1), is not strictly ascending or continues
+ *           after its -1 padding. Such a pattern scores -inf with span (-1, -1) and labels -1
+ *           on every row, its labels are never used as indices, and its
+ *           OCRK_STATUS_CTC_BAD_LENGTH / _BAD_LABEL bit is OR-ed into status_word (if given).
+ * No floating-point atomics: the whole call is reproducible bit for bit.
+ *   ws: >= ocrk_ctc_field_workspace_size(T, B, C, n_pat, max_pat_len) bytes, 16-B aligned (the
+ *       rel table and one word per pattern). */
+size_t ocrk_ctc_field_workspace_size(int T, int B, int C, int n_pat, int max_pat_len);
+int ocrk_ctc_field(const float* logits, const int* seq_len, int T, int B, int C, const int* pat_cls,
+                   const int* pat_opt, const int* pat_len, int n_pat, int max_pat_len, float* score,
+                   int* span, int* text, int* pat_status, uint32_t* status_word, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* a10 -- validate._get_output (src/weinman/validate.py:81-92) =
  * tf.nn.ctc_greedy_decoder(logits, seq_len, merge_repeated) + sparse_to_dense(-1):
  *   out i64 [B, T] (labels then -1), out_len i32 [B], neg_sum_logits f32 [B] or NULL. */
