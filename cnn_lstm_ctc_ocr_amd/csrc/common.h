@@ -97,9 +97,12 @@ enum Option : int {
     OPT_LSTM_BWD_DMA,         // 1 (default): LDS-DMA staging in the per-step LSTM backward kernels
     OPT_LSTM_FWD_R16,         // 1 (default): 16-row / 64-unit members for the bf16 forward loop at H = 512
     OPT_NT_TAP_UNIFORM,       // 1 (default): the NT ring's tap-uniform im2col addressing where C % BK == 0
+    OPT_GEMM_W4,              // one-wave-per-SIMD 256 x 256 GEMM engines: 0 off, 1 (default) the measured routes, 2 every covered shape
+    OPT_GEMM_W4_LAUNCHES,     // debug counter: launches of those engines so far (tests; settable, e.g. to 0)
     OPT_COUNT
 };
 int64_t opt(Option o);
+void opt_add(Option o, int64_t d);   // counters kept in the registry (GEMM_W4_LAUNCHES)
 
 }  // namespace ocrk
 

@@ -89,6 +89,13 @@ bool f32_exact_mfma();
 // -1 when it does not cover the call. OCRK_GEMM_PP=0 disables it.
 int gemm_pp(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
 
+// One-wave-per-SIMD 256 x 256 x 64 engines (4 waves, a 128 x 128 register tile each): gemm_w4
+// takes gemm_pp's plain A_ROWK x B_NK calls (gemm_w4.hip), gemm_w4tn gemm_pptn's A_COLK x B_KN
+// calls (gemm_w4tn.hip), bit-identical to them. Option GEMM_W4: 0 off, 1 the measured routes,
+// 2 every covered shape. -1 when not routed or not covered.
+int gemm_w4(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
+int gemm_w4tn(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
+
 // 8-wave ping-pong engine for A_COLK x B_KN weight gradients (gemm_pptn.hip),
 // f32 C or split-K partials, M, N >= 256. -1 when not covered (OCRK_GEMM_PPTN=0).
 bool gemm_pptn_covers(int amode, int M, int N, int convC);   // shape test of gemm_pptn (wgrad split choice)

@@ -599,9 +599,12 @@ int gemm(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t strea
         OCRK_REQUIRE(st >= 0, "gemm: ReLU bit masks need the NT engine (bf16 C, staged epilogue) for this shape");
         return st;
     }
-    int nt = gemm_pp(p, amode, bmode, dtype, stream);
+    // the one-wave-per-SIMD engines are asked first (option GEMM_W4; -1: not routed / not covered)
+    int nt = gemm_w4(p, amode, bmode, dtype, stream);
+    if (nt < 0) nt = gemm_pp(p, amode, bmode, dtype, stream);
     if (nt >= 0) return nt != OCRK_OK ? nt : splitk_finish(p, stream);
     nt = gemm_nt(p, amode, bmode, dtype, stream);
+    if (nt < 0) nt = gemm_w4tn(p, amode, bmode, dtype, stream);
     if (nt < 0) nt = gemm_pptn(p, amode, bmode, dtype, stream);
     if (nt < 0) nt = gemm_tn(p, amode, bmode, dtype, stream);
     if (nt >= 0) return nt != OCRK_OK ? nt : splitk_finish(p, stream);

@@ -84,24 +84,6 @@ template <int N> __device__ __forceinline__ void vm_wait_nop() {}
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 
-// work item w -> (output tile, z = batch * splits + slice); tiles in groups
-// of 4 row-tiles x all column-tiles (row-tile fastest) so the items an XCD
-// runs at once share A rows and B columns in its L2
-struct PPItem { int m0, n0, zb, zs; };
-__device__ __forceinline__ PPItem pp_item(int w, int tm, int tn, int splits, int BM, int BN) {
-    const int nT = tm * tn;
-    const int z = w / nT, t = w - z * nT;
-    constexpr int GM = 4;
-    const int gsz = GM * tn, grp = t / gsz, first = grp * GM;
-    const int gm = min(GM, tm - first), r = t - grp * gsz;
-    PPItem it;
-    it.m0 = (first + r % gm) * BM;
-    it.n0 = (r / gm) * BN;
-    it.zb = z / splits;
-    it.zs = z - it.zb * splits;
-    return it;
-}
-
 template <int AM, int BN, bool STATS, bool MASK>
 __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmParams p) {
     constexpr int BM = 256, BK = 64, ROWB = 128;          // 64 bf16 = 128 B per LDS row
@@ -487,30 +469,6 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(const GemmParams p) {
             for (int j = 0; j < 2 * QN; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
         if (wm == 1) pp_barrier();                        // re-stagger
     }
-}
-
-// s_waitcnt vmcnt(n) for a wave-uniform runtime count (the in-flight VMEM ops a
-// schedule allows): a scalar jump table over the immediate forms; n > 63 waits
-// for vmcnt(63), which is stricter and so still correct.
-__device__ __forceinline__ void vm_wait_n(int n) {
-    n = __builtin_amdgcn_readfirstlane(n);
-    n = n > 63 ? 63 : n;
-    switch (n) {
-#define VW1(i) case i: vm_wait<i>(); break;
-#define VW8(b) VW1(b) VW1(b + 1) VW1(b + 2) VW1(b + 3) VW1(b + 4) VW1(b + 5) VW1(b + 6) VW1(b + 7)
-        VW8(0) VW8(8) VW8(16) VW8(24) VW8(32) VW8(40) VW8(48) VW8(56)
-#undef VW8
-#undef VW1
-    default: vm_wait<0>();
-    }
-}
-
-// vm_wait_n with the schedule's steady-state count as a one-compare fast path
-template <int FAST>
-__device__ __forceinline__ void vm_wait_fast(int n) {
-    n = __builtin_amdgcn_readfirstlane(n);
-    if (n == FAST) vm_wait<FAST>();
-    else vm_wait_n(n);
 }
 
 // ---------------------------------------------------------------------------

@@ -156,4 +156,48 @@ __device__ __forceinline__ void lds_dma16_asm(const i32x4_t& r, void* lds, unsig
                  :: "v"(voff), "s"(r), "{m0}"(a) : "memory");
 }
 
+// ---- shared by the 256-row tile engines (gemm_pp.hip, gemm_w4.hip, gemm_w4tn.hip)
+
+// work item w -> (output tile, z = batch * splits + slice); tiles in groups
+// of 4 row-tiles x all column-tiles (row-tile fastest) so the items an XCD
+// runs at once share A rows and B columns in its L2
+struct PPItem { int m0, n0, zb, zs; };
+__device__ __forceinline__ PPItem pp_item(int w, int tm, int tn, int splits, int BM, int BN) {
+    const int nT = tm * tn;
+    const int z = w / nT, t = w - z * nT;
+    constexpr int GM = 4;
+    const int gsz = GM * tn, grp = t / gsz, first = grp * GM;
+    const int gm = min(GM, tm - first), r = t - grp * gsz;
+    PPItem it;
+    it.m0 = (first + r % gm) * BM;
+    it.n0 = (r / gm) * BN;
+    it.zb = z / splits;
+    it.zs = z - it.zb * splits;
+    return it;
+}
+
+// s_waitcnt vmcnt(n) for a wave-uniform runtime count (the in-flight VMEM ops a
+// schedule allows): a scalar jump table over the immediate forms; n > 63 waits
+// for vmcnt(63), which is stricter and so still correct.
+__device__ __forceinline__ void vm_wait_n(int n) {
+    n = __builtin_amdgcn_readfirstlane(n);
+    n = n > 63 ? 63 : n;
+    switch (n) {
+#define VW1(i) case i: vm_wait<i>(); break;
+#define VW8(b) VW1(b) VW1(b + 1) VW1(b + 2) VW1(b + 3) VW1(b + 4) VW1(b + 5) VW1(b + 6) VW1(b + 7)
+        VW8(0) VW8(8) VW8(16) VW8(24) VW8(32) VW8(40) VW8(48) VW8(56)
+#undef VW8
+#undef VW1
+    default: vm_wait<0>();
+    }
+}
+
+// vm_wait_n with the schedule's steady-state count as a one-compare fast path
+template <int FAST>
+__device__ __forceinline__ void vm_wait_fast(int n) {
+    n = __builtin_amdgcn_readfirstlane(n);
+    if (n == FAST) vm_wait<FAST>();
+    else vm_wait_n(n);
+}
+
 }  // namespace ocrk

@@ -93,7 +93,7 @@ const char* ocrk_last_error(void);
  * NT_F32_MASK, NT_F32_X6, BEAM_WAVE, BN_BWD_BLOCKS, BN_ROUTE, BN_ROUTE_SEG,
  * BN_ROUTE_NCH, CONV_TN_ITEMS, CONV_TN4_ITEMS,
  * CONV_WGRAD_CUS, F32_MFMA, GEMM_NT, GEMM_NT_STAGED, GEMM_PP, GEMM_PPTN, PP_MIN_N, GEMM_TN, LSTM_DMA,
- * LSTM_BWD_DMA, LSTM_FWD_R16, NT_TAP_UNIFORM (meanings in csrc/common.h). Unknown name: OCRK_ERR_INVALID_ARG.
+ * LSTM_BWD_DMA, LSTM_FWD_R16, NT_TAP_UNIFORM, GEMM_W4, GEMM_W4_LAUNCHES (meanings in csrc/common.h). Unknown name: OCRK_ERR_INVALID_ARG.
  * `prev` may be NULL. (LSTM_BWD_KSPLIT, LSTM_BWD_PB16 and PP_DEEP: the tools build
  * only -- routes measured slower, not compiled into this library.) */
 int ocrk_set_option(const char* name, int64_t value, int64_t* prev);

@@ -5,6 +5,9 @@ tests/).
 
     python tools/bench_pp.py                 # default routing (engine on)
     OCRK_GEMM_PP=0 python tools/bench_pp.py  # previous engines (hipBLASLt / NT)
+    python tools/bench_pp.py --ab [reps]     # the plain GEMMs, GEMM_W4=0 against GEMM_W4=2 (the
+                                             # one-wave-per-SIMD engine, csrc/gemm_w4.hip): interleaved in
+                                             # this process, `reps` (5) repetitions of 20 launches each
 """
 import os
 import sys
@@ -36,7 +39,42 @@ def rel(x, ref):
     return float((x.float() - ref).norm() / ref.norm().clamp_min(1e-30))
 
 
+PLAIN = [(32000, 4096, 256, "proj L1"), (32000, 4096, 1024, "proj L2"), (32000, 1024, 4096, "dx L2"),
+         (32000, 256, 4096, "dx L1"), (32000, 1024, 96, "logits dx")]
+
+
+def ab_w4(reps):
+    """Old and new engine interleaved; a shape is won if the new engine's slowest repetition beats
+    the old engine's fastest."""
+    from cnn_lstm_ctc_ocr_amd import options
+    torch.manual_seed(0)
+    dev = torch.device("cuda")
+    bf = torch.bfloat16
+    print(f"{'shape':12s} {'engine':8s} {'min us':>9s} {'max us':>9s} {'TFLOP/s (min)':>14s}   repetitions (us)")
+    for (M, N, Kd, tag) in PLAIN:
+        a = (torch.rand(M, Kd, device=dev) * 2 - 1).to(bf)
+        w = ((torch.rand(N, Kd, device=dev) * 2 - 1) * 0.05).to(bf)
+        bias = torch.randn(N, device=dev) if "proj" in tag else None
+        f = lambda: K.gemm(a, w, trans_b=True, bias=bias, out_dtype=bf)  # noqa: E731
+        t = {0: [], 2: []}
+        outs = {}
+        for _ in range(reps):
+            for mode in (0, 2):
+                with options.override(GEMM_W4=mode):
+                    outs[mode] = f()
+                    t[mode].append(timed(f) * 1e3)
+        same = torch.equal(outs[0], outs[2])
+        for mode, name in ((0, "old"), (2, "w4")):
+            v = t[mode]
+            print(f"{tag:12s} {name:8s} {min(v):9.1f} {max(v):9.1f} {2.0 * M * N * Kd / min(v) / 1e6:14.1f}   "
+                  + " ".join(f"{x:.1f}" for x in v))
+        print(f"{tag:12s} {'won' if max(t[2]) < min(t[0]) else 'not won'}; bit-identical: {same}", flush=True)
+
+
 def main():
+    if "--ab" in sys.argv:
+        i = sys.argv.index("--ab")
+        return ab_w4(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 5)
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     torch.manual_seed(0)
     dev = torch.device("cuda")

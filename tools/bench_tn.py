@@ -1,5 +1,9 @@
 """Weight-gradient (TN) GEMMs of the train step: time per call and TFLOP/s on
-the engine the dispatcher picks (OCRK_GEMM_PPTN=0: the 4-wave engine)."""
+the engine the dispatcher picks (OCRK_GEMM_PPTN=0: the 4-wave engine).
+
+    python tools/bench_tn.py --ab [reps]   # GEMM_W4=0 against GEMM_W4=2 (the one-wave-per-SIMD engine,
+                                           # csrc/gemm_w4tn.hip), interleaved, `reps` (5) repetitions each
+"""
 import os
 import sys
 
@@ -11,9 +15,58 @@ from cnn_lstm_ctc_ocr_amd.model import _splits  # noqa: E402
 
 R = 32000
 dev = torch.device("cuda")
+SHAPES = [(1024, 2048, 4096, "L2 dW_x (per dir)"), (512, 2048, 4096, "dW_h (per dir)"),
+          (256, 2048, 4096, "L1 dW_x (per dir)"), (1024, 96, 96, "logits dW")]
+
+
+def _timed(f, n=10):
+    f()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(n):
+        f()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def ab_w4(reps):
+    """Old and new engine interleaved (split-K reduce included in both); a shape is won if the new
+    engine's slowest repetition beats the old engine's fastest."""
+    from cnn_lstm_ctc_ocr_amd import options
+    print(f"{'shape':20s} {'engine':6s} {'min us':>9s} {'max us':>9s} {'TFLOP/s (min)':>14s}   repetitions (us)")
+    for n_in, N, ldb, tag in SHAPES:
+        x = (torch.rand(R, n_in, device=dev) * 2 - 1).bfloat16()
+        dG = (torch.rand(R, ldb, device=dev) * 2 - 1).bfloat16()
+        sp = _splits(n_in, N, R)
+        t = {0: [], 2: []}
+        outs = {}
+        for _ in range(reps):
+            for mode in (0, 2):
+                with options.override(GEMM_W4=mode):
+                    gk = torch.zeros(n_in, N, device=dev)
+                    f = lambda: K.gemm(x, dG, trans_a=True, out=gk, accumulate=True, M=n_in, N=N, K=R,  # noqa: E731
+                                       lda=n_in, ldb=ldb, ldc=N, splits=sp)
+                    f()
+                    outs[mode] = gk.clone()
+                    t[mode].append(_timed(f) * 1e3)
+        same = torch.equal(outs[0], outs[2])
+        for mode, name in ((0, "old"), (2, "w4")):
+            v = t[mode]
+            print(f"{tag:20s} {name:6s} {min(v):9.1f} {max(v):9.1f} {2.0 * n_in * N * R / min(v) / 1e6:14.1f}   "
+                  + " ".join(f"{q:.1f}" for q in v))
+        print(f"{tag:20s} splits {sp}: {'won' if max(t[2]) < min(t[0]) else 'not won'}; bit-identical: {same}",
+              flush=True)
+
+
+if "--ab" in sys.argv:
+    _i = sys.argv.index("--ab")
+    ab_w4(int(sys.argv[_i + 1]) if len(sys.argv) > _i + 1 else 5)
+    sys.exit(0)
+
 tot = 0.0
-for n_in, N, ldb, tag in [(1024, 2048, 4096, "L2 dW_x (per dir)"), (512, 2048, 4096, "dW_h (per dir)"),
-                          (256, 2048, 4096, "L1 dW_x (per dir)"), (1024, 96, 96, "logits dW")]:
+for n_in, N, ldb, tag in SHAPES:
     x = (torch.rand(R, n_in, device=dev) * 2 - 1).bfloat16()
     dG = (torch.rand(R, ldb, device=dev) * 2 - 1).bfloat16()
     gk = torch.zeros(n_in, N, device=dev)

@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC passes over one GEMM shape (tools/pp_one.py), one rocprofv3 run per counter set.
 #   bash tools/pmc_pp.sh TAG M N K
+# OCRK_GEMM_W4=2 in the environment runs the same passes on the one-wave-per-SIMD engines.
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/pmc_$tag

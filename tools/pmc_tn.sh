@@ -1,6 +1,7 @@
 #!/bin/bash
 # SQ / LDS counter passes over one batched TN weight-gradient GEMM (tools/tn_one.py).
 #   bash tools/pmc_tn.sh TAG M N
+# OCRK_GEMM_W4=2 in the environment runs the same passes on the one-wave-per-SIMD engines.
 set -o pipefail
 tag=$1; shift
 out=gpurun_out/pmc_$tag

@@ -1,6 +1,7 @@
 """Run one GEMM shape through K.gemm a few times (for rocprofv3 counter passes).
 
     python tools/pp_one.py M N K [reps]
+    OCRK_GEMM_W4=2 python tools/pp_one.py M N K [reps]   # the one-wave-per-SIMD engine (csrc/gemm_w4.hip)
 """
 import os
 import sys

@@ -1,6 +1,7 @@
 """Run one batched weight-gradient (TN) GEMM as the train step issues it (for
 rocprofv3 counter passes):  python tools/tn_one.py M N [reps]
-(K = T*B = 32000, both directions as batch 2 over a [K][2N] dG, f32 C)."""
+(K = T*B = 32000, both directions as batch 2 over a [K][2N] dG, f32 C).
+OCRK_GEMM_W4=2 in the environment selects the one-wave-per-SIMD engine (csrc/gemm_w4tn.hip)."""
 import os
 import sys
 
