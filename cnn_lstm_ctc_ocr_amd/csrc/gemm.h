@@ -90,8 +90,9 @@ bool f32_exact_mfma();
 int gemm_pp(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
 
 // One-wave-per-SIMD 256 x 256 x 64 engines (4 waves, a 128 x 128 register tile each): gemm_w4
-// takes gemm_pp's plain A_ROWK x B_NK calls (gemm_w4.hip), gemm_w4tn gemm_pptn's A_COLK x B_KN
-// calls (gemm_w4tn.hip), bit-identical to them. Option GEMM_W4: 0 off, 1 the measured routes,
+// takes gemm_pp's plain A_ROWK x B_NK calls (gemm_w4.hip; a 256 x 128 tile where 256 x 256 items
+// would cover at most half of the CUs), gemm_w4tn gemm_pptn's A_COLK / A_IM2COL_T x B_KN calls
+// (gemm_w4tn.hip), bit-identical to them. Option GEMM_W4: 0 off, 1 the measured routes,
 // 2 every covered shape. -1 when not routed or not covered.
 int gemm_w4(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
 int gemm_w4tn(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);

@@ -118,13 +118,23 @@ __device__ __forceinline__ void w4_dma16(const i32x4_t& r, unsigned lds, unsigne
                  :: "v"(voff), "s"(r), "s"(soff), "{m0}"(lds) : "memory");
 }
 
+// BN = 256: the geometry above. BN = 128, for calls whose 256 x 256 items would leave half of the
+// CUs idle: a 256 x 128 tile, the waves still 2 x 2, each a 128 x 64 tile (acc[8][4]); UB is 128
+// rows (4 pieces per wave), a K-tile buffer 48 KB, the clusters half as many MFMAs around the
+// same barriers (K0: 32 | 12 reads, K1a: 16 | 8 A reads | UA, K1b: 16 | 4 B reads | UB). Two
+// buffers as well: a ring of three (144 KB, staged three K-tiles ahead) measured the same on the
+// layer-1 data gradient, 89.6-93.5 against 91.9-93.6 us (profiles/w4conv_gemm_bench.txt).
+template <int BN>
 __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
-    constexpr int BM = 256, BN = 256, BK = 64, ROWB = 128;
+    constexpr int BM = 256, BK = 64, ROWB = 128;
+    constexpr int WN = BN / 2, NJ = WN / 16;              // wave tile: 128 rows x WN columns, NJ B fragments
     constexpr int A_BYTES = BM * ROWB, BUF = (BM + BN) * ROWB;
-    constexpr int NU = 8;                                 // DMA instructions per wave per unit
-    constexpr int BIAS_OFF = 2 * BUF, STG_OFF = BIAS_OFF + 4 * 1024;
-    constexpr int PITCH = 128 * 2 + 16, STG = 16 * PITCH; // staging: 16 rows x 128 columns per wave
-    constexpr int NST = 8 * 4;                            // 16-B C stores per lane per item
+    constexpr int NU = 8, NUB = BN / 32;                  // DMA instructions per wave per unit (UA, UB)
+    constexpr int NB = 2;                                 // K-tile buffers (tile s in buffer s & 1)
+    constexpr int BIAS_OFF = NB * BUF, STG_OFF = BIAS_OFF + 4 * 1024;
+    constexpr int PITCH = WN * 2 + 16, STG = 16 * PITCH;  // staging: 16 rows x WN columns per wave
+    constexpr int CL = WN / 8, RPS = 64 / CL;             // lanes per staged row, rows per store instruction
+    constexpr int NST = 8 * (16 / RPS);                   // 16-B C stores per lane per item
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -197,7 +207,7 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
             KArgs e = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(e));
             const i32x4_t rbias = w4_rsrc(e->bias + i_zb * e->strideBias, p.N * 4);
-            w4_dma16(rbias, lds0 + BIAS_OFF + (i_cnt & 3) * 1024, on && n < p.N ? (unsigned)(n * 4) : W4_OOB, 0u);
+            w4_dma16(rbias, lds0 + BIAS_OFF + (i_cnt & 3) * 1024, on && 4 * lane < BN && n < p.N ? (unsigned)(n * 4) : W4_OOB, 0u);
             ops += 1;
         }
     };
@@ -214,44 +224,43 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
     // ---- compute side
     int w_comp = w_issue, c_cnt = 0;
 
-    bf16x8 af0[8], bf0[8], af1[8], bf1[8];                // fragments of kk = 0 / kk = 1
-    const int a_base = (wm * 128 + i16) * ROWB, b_base = A_BYTES + (wn * 128 + i16) * ROWB;
+    bf16x8 af0[8], bf0[NJ], af1[8], bf1[NJ];              // fragments of kk = 0 / kk = 1
+    const int a_base = (wm * 128 + i16) * ROWB, b_base = A_BYTES + (wn * WN + i16) * ROWB;
     auto read_a = [&](const char* buf, int kk, bf16x8 (&fr)[8]) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             fr[i] = *reinterpret_cast<const bf16x8*>(buf + a_base + i * 16 * ROWB + (((kk * 4 + g) ^ sw) << 4));
     };
-    auto read_b = [&](const char* buf, int kk, bf16x8 (&fr)[8]) {
+    auto read_b = [&](const char* buf, int kk, bf16x8 (&fr)[NJ]) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
+        for (int j = 0; j < NJ; ++j)
             fr[j] = *reinterpret_cast<const bf16x8*>(buf + b_base + j * 16 * ROWB + (((kk * 4 + g) ^ sw) << 4));
     };
-    floatx4 acc[8][8];
+    floatx4 acc[8][NJ];
     auto zero_acc = [&]() {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < NJ; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
     };
-    auto mfma_rows = [&](auto I0_, const bf16x8 (&a)[8], const bf16x8 (&b)[8]) {
+    auto mfma_rows = [&](auto I0_, const bf16x8 (&a)[8], const bf16x8 (&b)[NJ]) {
         constexpr int I0 = decltype(I0_)::value;          // acc rows I0 .. I0 + 3
 #pragma unroll
         for (int i = I0; i < I0 + 4; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
+            for (int j = 0; j < NJ; ++j)
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
     };
     using R0 = std::integral_constant<int, 0>;
     using R4 = std::integral_constant<int, 4>;
     (void)read_b;
 
-    // ---- prologue: K-tiles 0 and 1 of the stream; tile 0 landed, its kk = 0 fragments read
-    int mA1 = 0, mB1 = 0, mA2 = 0, mB2 = 0;               // tallies behind UA / UB of tiles s+1, s+2
+    // ---- prologue: K-tiles 0 .. NB-1 of the stream; tile 0 landed, its kk = 0 fragments read
+    int mA[NB + 1] = {}, mB[NB + 1] = {};                 // [d]: tallies behind UA / UB of tile s+d
     setup_issue(w_issue);
     bool more = true;
-    int m0done = 0;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int t = 0; t < NB; ++t) {
         const unsigned va = lane_off(a_lane, more), vb = lane_off(b_lane, more);
         int row;
         unsigned lds;
@@ -259,17 +268,16 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) dma_a(i, row, lds, va);
         ops += NU;
-        mA1 = ops;
+        mA[t] = ops;
         dma_bias(more);
         unit_base(i_n0, lds0 + t * BUF + A_BYTES, row, lds);
 #pragma unroll
-        for (int i = 0; i < NU; ++i) dma_b(i, row, lds, vb);
-        ops += NU;
-        mB1 = ops;
-        if (t == 0) m0done = ops;
+        for (int i = 0; i < NUB; ++i) dma_b(i, row, lds, vb);
+        ops += NUB;
+        mB[t] = ops;
         if (more) more = advance_issue();
     }
-    vm_wait_n(ops - m0done);
+    vm_wait_n(ops - mB[0]);
     w4_barrier();
     read_a(smem, 0, af0);
     read_b(smem, 0, bf0);
@@ -287,12 +295,13 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
         read_b(cur, 1, bf1);
         mfma_rows(R0{}, af0, bf0);
         mfma_rows(R4{}, af0, bf0);
-        w4_interleave<16, 3, 16>();
+        if constexpr (NJ == 8) w4_interleave<16, 3, 16>();    // 64 MFMAs | 16 reads
+        else w4_interleave<12, 2, 8>();                       // 32 MFMAs | 12 reads
         __builtin_amdgcn_s_setprio(0);
         // ---- P: tile s fully read (WAR), UA(s+1) landed (RAW)
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        vm_wait_fast<NU>(ops - mA1);
+        vm_wait_fast<NUB>(ops - mA[1]);                       // UB(s+1) stays in flight
         w4_barrier();
         // ---- K1a: kk = 1, acc rows 0-3 | A reads of tile s+1 | UA(s+2) into buffer s & 1
         // (past the stream's end the reads return stale bytes that nothing consumes, and the
@@ -307,17 +316,18 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
             for (int q = 0; q < 8; ++q) {
                 af0[q] = *reinterpret_cast<const bf16x8*>(nxt + a_base + q * 16 * ROWB + ((g ^ sw) << 4));
 #pragma unroll
-                for (int j = (q & 1) * 4; j < (q & 1) * 4 + 4; ++j)
-                    acc[q >> 1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf1[j], af1[q >> 1], acc[q >> 1][j], 0, 0, 0);
+                for (int t = q * (NJ / 2); t < (q + 1) * (NJ / 2); ++t)   // NJ / 2 of the 4 NJ MFMAs per read
+                    acc[t / NJ][t % NJ] =
+                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf1[t % NJ], af1[t / NJ], acc[t / NJ][t % NJ], 0, 0, 0);
                 dma_a(q, row, lds, va);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __builtin_amdgcn_s_setprio(0);
             ops += NU;
-            mA2 = ops;
+            mA[NB] = ops;
         }
         // ---- M: UB(s+1) landed
-        vm_wait_fast<NU>(ops - mB1);
+        vm_wait_fast<NU>(ops - mB[1]);                        // UA(s+2) stays in flight
         w4_barrier();
         // ---- K1b: kk = 1, acc rows 4-7 | B reads of tile s+1 | UB(s+2)
         {
@@ -328,22 +338,22 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
             unit_base(i_n0, lds0 + (s & 1) * BUF + A_BYTES, row, lds);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
+            for (int q = 0; q < NJ; ++q) {
                 bf0[q] = *reinterpret_cast<const bf16x8*>(nxt + b_base + q * 16 * ROWB + ((g ^ sw) << 4));
 #pragma unroll
-                for (int j = (q & 1) * 4; j < (q & 1) * 4 + 4; ++j)
-                    acc[4 + (q >> 1)][j] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf1[j], af1[4 + (q >> 1)], acc[4 + (q >> 1)][j], 0, 0, 0);
+                for (int t = q * 4; t < q * 4 + 4; ++t)       // 4 of the 4 NJ MFMAs per read
+                    acc[4 + t / NJ][t % NJ] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf1[t % NJ], af1[4 + t / NJ],
+                                                                                      acc[4 + t / NJ][t % NJ], 0, 0, 0);
                 dma_b(q, row, lds, vb);
                 __builtin_amdgcn_sched_barrier(0);
             }
             __builtin_amdgcn_s_setprio(0);
-            ops += NU;
-            mB2 = ops;
+            ops += NUB;
+            mB[NB] = ops;
         }
         if (more) more = advance_issue();
-        mA1 = mA2;
-        mB1 = mB2;
+        mA[1] = mA[2];
+        mB[1] = mB[2];
         ++s;
       }
 
@@ -358,25 +368,25 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
             asm volatile("" : "+s"(e));
             const int i16 = el & 15, g = el >> 4;
             // bias (the item's LDS slot: 0 past N; zeros without bias)
-            const char* bslot = smem + BIAS_OFF + (c_cnt & 3) * 1024 + (wn * 128 + 4 * g) * 4;
-            floatx4 bv[8];
+            const char* bslot = smem + BIAS_OFF + (c_cnt & 3) * 1024 + (wn * WN + 4 * g) * 4;
+            floatx4 bv[NJ];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
+            for (int j = 0; j < NJ; ++j) {
                 bv[j] = floatx4{0.f, 0.f, 0.f, 0.f};
                 if (has_bias) bv[j] = *reinterpret_cast<const floatx4*>(bslot + j * 64);
             }
             // bf16 C through the wave's staging area, 16 rows per slice: each store
-            // instruction writes 4 rows x 256 B at 16 B per lane
+            // instruction writes RPS rows x 2 WN bytes at 16 B per lane
             char* stg = smem + STG_OFF + wave * STG;
             bf16* Cb = reinterpret_cast<bf16*>(e->C) + cur_it.zb * e->strideC;
             const __amdgpu_buffer_rsrc_t rc =
                 __builtin_amdgcn_make_buffer_rsrc(Cb, 0, ((p.M - 1) * (int)e->ldc + p.N) * 2, 0x00020000);
-            const int c8 = el & 15, r0 = el >> 4;
-            const int n = cur_it.n0 + wn * 128 + 8 * c8;
+            const int c8 = el & (CL - 1), r0 = el / CL;
+            const int n = cur_it.n0 + wn * WN + 8 * c8;
 #pragma unroll
             for (int h = 0; h < 8; ++h) {
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
+                for (int j = 0; j < NJ; ++j) {
                     floatx4 v = acc[h][j] * e->alpha + bv[j];          // gemm_pp's epilogue expression
                     if (e->relu) {
 #pragma unroll
@@ -389,8 +399,8 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
                 }
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = r0 + q * 4;
+                for (int q = 0; q < 16 / RPS; ++q) {
+                    const int r = r0 + q * RPS;
                     const int m = cur_it.m0 + wm * 128 + h * 16 + r;
                     const u32x4 v = *reinterpret_cast<const u32x4*>(stg + r * PITCH + c8 * 16);
                     const unsigned off = (m < p.M && n < p.N) ? (unsigned)(((int64_t)m * e->ldc + n) * 2) : W4_OOB;
@@ -428,18 +438,27 @@ int gemm_w4(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t st
     //   proj L2 32000 x 4096 x 1024   266.5-330.9 -> 252.0-278.2   ranges overlap
     //   proj L1 32000 x 4096 x 256     96.9-111.8 ->  97.3-121.8   equal
     //   dx L1   32000 x 256 x 4096     77.0-80.2  -> 107.8-114.7   slower (125 items on 256 CUs; NT engine)
+    // and on the 256 x 128 tile (profiles/w4conv_gemm_bench.txt, NT engine -> this engine):
+    //   dx L1   32000 x 256 x 4096     80.8-82.7  ->  91.9-93.6    slower (250 items): not routed
     // 2: every covered shape
     if (mode == 1 && (p.K < 2048 || p.N < 512)) return -1;
-    constexpr int LDS = 2 * 512 * 128 + 4 * 1024 + 4 * 16 * (128 * 2 + 16);
-    static DeviceOnce configured;
-    set_dyn_lds(configured, reinterpret_cast<const void*>(&gemm_w4_kernel), LDS);
     const int ncu = cu_count();
-    const int64_t items = cdiv(p.M, 256) * cdiv(p.N, 256) * (int64_t)p.batch;
+    // the 256 x 128 tile where 256 x 256 items would cover at most half of the CUs (one round
+    // either way, of items half as long)
+    const bool narrow = 2 * cdiv(p.M, 256) * cdiv(p.N, 256) * (int64_t)p.batch <= ncu;
+    const int bn = narrow ? 128 : 256;
+    const int lds = 2 * (256 + bn) * 128 + 4 * 1024 + 4 * 16 * (bn + 16);
+    static DeviceOnce configured[2];
+    const void* kern = narrow ? reinterpret_cast<const void*>(&gemm_w4_kernel<128>)
+                              : reinterpret_cast<const void*>(&gemm_w4_kernel<256>);
+    set_dyn_lds(configured[narrow ? 1 : 0], kern, lds);
+    const int64_t items = cdiv(p.M, 256) * cdiv(p.N, bn) * (int64_t)p.batch;
     // persistent always (one workgroup per CU): the K-tile stream runs across items, so an item's
     // prologue is staged under the previous item's last K-tiles, and the epilogue's stores are in
     // the tally, never in front of a wait
     const int64_t grid = std::min<int64_t>(cdiv(items, 8) * 8, (int64_t)(ncu / 8) * 8);
-    gemm_w4_kernel<<<dim3((unsigned)grid), 256, LDS, stream>>>(p);
+    if (narrow) gemm_w4_kernel<128><<<dim3((unsigned)grid), 256, lds, stream>>>(p);
+    else gemm_w4_kernel<256><<<dim3((unsigned)grid), 256, lds, stream>>>(p);
     opt_add(OPT_GEMM_W4_LAUNCHES, 1);
     return launch_status("gemm_w4");
 }

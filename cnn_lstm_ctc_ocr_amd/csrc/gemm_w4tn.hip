@@ -6,6 +6,10 @@
 // weight gradients dW = x^T dG, h_prev^T dG over the T*B time-major rows
 // (model_bu.py:167-199 / model.py:216-220), K = T*B, batched over the two
 // directions, split K into f32 partials (reduced by gemm.hip's splitk_finish).
+// AM = A_IM2COL_T takes gemm_pptn's other mode on the same schedule: the conv
+// weight gradient dW[(kh,kw,c)][cout] = im2col(x)^T . dy over the B*H*W pixels
+// for Cin % 64 == 0 and Cout >= 256 (conv7, conv8), where the A operand is
+// gathered from the NHWC input (see the A_IM2COL_T block in the kernel).
 //
 // The geometry and the schedule are gemm_w4.hip's (read it first): a 256 x 256
 // x 64 tile per 256-thread workgroup, 4 waves as 2 x 2, one per SIMD, a 128 x
@@ -62,7 +66,9 @@ __device__ __forceinline__ void w4t_dma16(const i32x4_t& r, unsigned lds, unsign
                  :: "v"(voff), "s"(r), "s"(soff), "{m0}"(lds) : "memory");
 }
 
+template <int AM>
 __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
+    constexpr bool IM = AM == A_IM2COL_T;
     constexpr int BM = 256, BN = 256, BK = 64, ROWB = 128, BLK = BK * ROWB;   // 8-KB [64 k][64 col] block
     constexpr int A_BYTES = 4 * BLK, BUF = 8 * BLK;
     constexpr int NU = 8;                                 // DMA instructions per wave per unit
@@ -92,7 +98,8 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
     // descriptors from uniform words (kernel arguments and the item); byte counts < 2^31 (launcher)
     const uint64_t pa = (uint64_t)(reinterpret_cast<const bf16*>(p.A) + zb * p.strideA);
     const uint64_t pb = (uint64_t)(reinterpret_cast<const bf16*>(p.B) + zb * p.strideB);
-    const i32x4_t ra = {(int)(unsigned)pa, (int)((unsigned)(pa >> 32) & 0xffffu), p.K * (int)p.lda * 2, 0x00020000};
+    const i32x4_t ra = {(int)(unsigned)pa, (int)((unsigned)(pa >> 32) & 0xffffu),
+                        p.K * (IM ? p.convC : (int)p.lda) * 2, 0x00020000};
     const i32x4_t rb = {(int)(unsigned)pb, (int)((unsigned)(pb >> 32) & 0xffffu), p.K * (int)p.ldb * 2, 0x00020000};
 
     // ---- per-lane DMA geometry: piece i (0..7) of a wave's unit is block i >> 1, k-rows
@@ -107,12 +114,66 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         krow[h] = (h * 4 + wave) * 8 + lrow;
-        va[h] = (unsigned)((krow[h] * (int)p.lda + m0 + 8 * chunk) * 2);
+        va[h] = IM ? (unsigned)((krow[h] * p.convC + 8 * chunk) * 2)
+                   : (unsigned)((krow[h] * (int)p.lda + m0 + 8 * chunk) * 2);
         vb[h] = (unsigned)((krow[h] * (int)p.ldb + n0 + 8 * chunk) * 2);
     }
+    // A_IM2COL_T (gemm_pptn's im2col A block): k is a pixel of the NHWC input and a 64-column block
+    // is 64 channels of one tap (Cin % 64 == 0; tap and first channel uniform per item), so a k-row
+    // of a block is 128 contiguous bytes at the shifted pixel, or zeros where the tap leaves the
+    // image. Per block: the tap's bit (0 for a block past M) and the byte shift of its source.
+    // Per lane: the two pixels (row ph, column pw) of the K-tile to be issued next, stepped by 64
+    // pixels per K-tile without a division, and the 9-bit mask of their taps inside the image.
+    // The whole source offset is per lane (no scalar part): alone, a tap's shift may be negative.
+    unsigned t_bit[4] = {0, 0, 0, 0}, t_sh[4] = {0, 0, 0, 0};
+    int pw[2] = {0, 0}, ph[2] = {0, 0};
+    unsigned pmask[2] = {0, 0};
+    int step_w = 0, step_h = 0;
+    auto tap_mask = [&](int h) {
+        const unsigned cb = 2u | (pw[h] > 0 ? 1u : 0u) | (pw[h] < p.convW - 1 ? 4u : 0u);
+        pmask[h] = (cb << 3) | (ph[h] > 0 ? cb : 0u) | (ph[h] < p.convH - 1 ? cb << 6 : 0u);
+    };
+    if constexpr (IM) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int col = min(m0 + 64 * b, p.M - 1);
+            const int tap = col / p.convC;
+            t_bit[b] = m0 + 64 * b < p.M ? 1u << tap : 0u;
+            t_sh[b] = (unsigned)((((tap / 3 - 1) * p.convW + tap % 3 - 1) * p.convC + col - tap * p.convC) * 2);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int k = kbeg + krow[h];
+            pw[h] = k % p.convW;
+            ph[h] = (k / p.convW) % p.convH;
+            tap_mask(h);
+        }
+        step_w = BK % p.convW;
+        step_h = (BK / p.convW) % p.convH;
+    }
+    auto next_pixels = [&]() {                            // after UA of a K-tile: the next K-tile's pixels
+        if constexpr (IM) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                pw[h] += step_w;
+                const bool wrap = pw[h] >= p.convW;
+                pw[h] -= wrap ? p.convW : 0;
+                ph[h] += step_h + (wrap ? 1 : 0);
+                ph[h] -= ph[h] >= p.convH ? p.convH : 0;
+                tap_mask(h);
+            }
+        }
+    };
     // piece i of UA / UB of K-tile kt into the buffer at LDS address buf (on = false: all out of range)
     auto dma_a = [&](int i, int kt, unsigned buf, bool on) {
         const int k0 = kbeg + kt * BK;
+        if constexpr (IM) {
+            const int b = i >> 1, h = i & 1;
+            const bool ok = on && k0 + krow[h] < kend && (pmask[h] & t_bit[b]) != 0;
+            const unsigned base = (unsigned)(k0 * p.convC * 2) + t_sh[b];
+            w4t_dma16(ra, buf + b * BLK + (h * 4 + wave) * 1024, ok ? va[h] + base : W4T_OOB, 0u);
+            return;
+        }
         const bool ok = on && k0 + krow[i & 1] < kend && m0 + 64 * (i >> 1) + 8 * chunk < p.M;
         const unsigned soff = on ? (unsigned)(k0 * (int)p.lda * 2 + 128 * (i >> 1)) : 0u;
         w4t_dma16(ra, buf + (i >> 1) * BLK + ((i & 1) * 4 + wave) * 1024, ok ? va[i & 1] : W4T_OOB, soff);
@@ -153,6 +214,7 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
     for (int t2 = 0; t2 < 2; ++t2) {
 #pragma unroll
         for (int i = 0; i < NU; ++i) dma_a(i, t2, lds0 + t2 * BUF, t2 < nk);
+        next_pixels();
 #pragma unroll
         for (int i = 0; i < NU; ++i) dma_b(i, t2, lds0 + t2 * BUF, t2 < nk);
     }
@@ -208,6 +270,7 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
             dma_a(q, kt + 2, curl, more);
             __builtin_amdgcn_sched_barrier(0);
         }
+        next_pixels();
         __builtin_amdgcn_s_setprio(0);
         // ---- M: UB(kt+1) landed (UA(kt+2) stays in flight)
         vm_wait<NU>();
@@ -265,23 +328,34 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
 // Runs the one-wave-per-SIMD TN engine when GEMM_W4 routes the call to it; -1 otherwise.
 int gemm_w4tn(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream) {
     const int64_t mode = opt(OPT_GEMM_W4);
-    if (mode == 0 || dtype != OCRK_BF16 || amode != A_COLK || bmode != B_KN) return -1;
-    // gemm_pptn's A_COLK preconditions
+    const bool im = amode == A_IM2COL_T;
+    if (mode == 0 || dtype != OCRK_BF16 || (amode != A_COLK && !im) || bmode != B_KN) return -1;
+    // gemm_pptn's preconditions (A_IM2COL_T: Cin % 64 == 0, one problem)
     if (!gemm_pptn_covers(amode, p.M, p.N, p.convC)) return -1;
     if (p.c_bf16 || p.bias || p.relu || p.mask || p.stats) return -1;
-    if (p.ldb % 8 != 0 || p.lda % 8 != 0) return -1;
+    if (p.ldb % 8 != 0 || (!im && p.lda % 8 != 0)) return -1;
     if (p.splits == 1 && (p.ldc % 4 != 0 || (uintptr_t)p.C % 16 != 0 || p.strideC % 4 != 0)) return -1;
     if (p.splits > 1 && (uintptr_t)p.splitk_ws % 16 != 0) return -1;
-    if ((int64_t)p.K * p.lda * 2 >= (1ll << 31) || (int64_t)p.K * p.ldb * 2 >= (1ll << 31)) return -1;
+    // 32-bit source offsets (A_IM2COL_T: up to two K-tiles past K are formed, then discarded)
+    const int64_t a_bytes = im ? ((int64_t)p.K + 128) * p.convC * 2 : (int64_t)p.K * p.lda * 2;
+    if (a_bytes >= (1ll << 31) || (int64_t)p.K * p.ldb * 2 >= (1ll << 31)) return -1;
+    if (im && (p.batch != 1 || p.convH < 1 || p.convW < 1 || p.M != 9 * p.convC)) return -1;
     // GEMM_W4=1, the measured route = every covered shape: each recurrent weight gradient won
     // (profiles/w4_gemm_bench.txt, us per direction incl. the split-K reduce, 5 interleaved
     // repetitions, ping-pong -> this engine): L2 dW_x 1024 x 2048 x 32000 151.4-174.1 -> 123.1-139.3,
-    // dW_h 512 x 2048 91.8-102.5 -> 77.2-84.3, L1 dW_x 256 x 2048 57.9-60.7 -> 51.1-52.6
+    // dW_h 512 x 2048 91.8-102.5 -> 77.2-84.3, L1 dW_x 256 x 2048 57.9-60.7 -> 51.1-52.6;
+    // and each im2col conv weight gradient at B = 256 (profiles/w4conv_gemm_bench.txt, us per call
+    // incl. the split-K reduce): conv7 1152 x 256 x 96000 113.3-120.0 -> 80.2-83.8,
+    // conv8 2304 x 256 x 96000 185.5-199.3 -> 125.2-132.2
     constexpr int LDS = 2 * 8 * 64 * 128;
-    static DeviceOnce configured;
-    set_dyn_lds(configured, reinterpret_cast<const void*>(&gemm_w4tn_kernel), LDS);
+    static DeviceOnce configured[2];
+    const void* kern = im ? reinterpret_cast<const void*>(&gemm_w4tn_kernel<A_IM2COL_T>)
+                          : reinterpret_cast<const void*>(&gemm_w4tn_kernel<A_COLK>);
+    set_dyn_lds(configured[im ? 1 : 0], kern, LDS);
     const int64_t items = cdiv(p.M, 256) * cdiv(p.N, 256) * (int64_t)p.batch * p.splits;
-    gemm_w4tn_kernel<<<dim3((unsigned)(cdiv(items, 8) * 8)), 256, LDS, stream>>>(p);
+    const dim3 grid((unsigned)(cdiv(items, 8) * 8));
+    if (im) gemm_w4tn_kernel<A_IM2COL_T><<<grid, 256, LDS, stream>>>(p);
+    else gemm_w4tn_kernel<A_COLK><<<grid, 256, LDS, stream>>>(p);
     opt_add(OPT_GEMM_W4_LAUNCHES, 1);
     return launch_status("gemm_w4tn");
 }
