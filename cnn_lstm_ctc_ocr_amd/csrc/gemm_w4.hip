@@ -123,7 +123,8 @@ __device__ __forceinline__ void w4_dma16(const i32x4_t& r, unsigned lds, unsigne
 // rows (4 pieces per wave), a K-tile buffer 48 KB, the clusters half as many MFMAs around the
 // same barriers (K0: 32 | 12 reads, K1a: 16 | 8 A reads | UA, K1b: 16 | 4 B reads | UB). Two
 // buffers as well: a ring of three (144 KB, staged three K-tiles ahead) measured the same on the
-// layer-1 data gradient, 89.6-93.5 against 91.9-93.6 us (profiles/w4conv_gemm_bench.txt).
+// layer-1 data gradient, 89.6-93.5 against 91.9-93.6 us (profiles/w4conv_gemm_bench.txt; both
+// with the accumulator shuffling that profiles/w4acc_isa.txt describes still in the K loop).
 template <int BN>
 __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
     constexpr int BM = 256, BK = 64, ROWB = 128;
@@ -237,22 +238,6 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
             fr[j] = *reinterpret_cast<const bf16x8*>(buf + b_base + j * 16 * ROWB + (((kk * 4 + g) ^ sw) << 4));
     };
     floatx4 acc[8][NJ];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-    };
-    auto mfma_rows = [&](auto I0_, const bf16x8 (&a)[8], const bf16x8 (&b)[NJ]) {
-        constexpr int I0 = decltype(I0_)::value;          // acc rows I0 .. I0 + 3
-#pragma unroll
-        for (int i = I0; i < I0 + 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
-    };
-    using R0 = std::integral_constant<int, 0>;
-    using R4 = std::integral_constant<int, 4>;
     (void)read_b;
 
     // ---- prologue: K-tiles 0 .. NB-1 of the stream; tile 0 landed, its kk = 0 fragments read
@@ -283,9 +268,12 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
     read_b(smem, 0, bf0);
 
     int s = 0;
-    for (;;) {                                            // items
-      zero_acc();
-      for (int c_kt = 0; c_kt < c_nk; ++c_kt) {           // the item's K-tiles
+    // one K-tile of the stream. FIRST: the item's first K-tile, whose K0 MFMAs take the literal 0
+    // as C (fma(a, b, +0) is what a zeroed accumulator computed), so an item's accumulators are
+    // defined by their first MFMA -- no zeroing pass, and no value merged into the accumulator
+    // registers at the item boundary for the register allocator to shuffle around
+    auto k_tile = [&](auto FIRST_) {
+        constexpr bool FIRST = decltype(FIRST_)::value;
         char* cur = smem + (s & 1) * BUF;
         const char* nxt = smem + ((s + 1) & 1) * BUF;
         // ---- K0: kk = 0 of tile s | reads of kk = 1
@@ -293,8 +281,14 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
         __builtin_amdgcn_s_setprio(1);
         read_a(cur, 1, af1);
         read_b(cur, 1, bf1);
-        mfma_rows(R0{}, af0, bf0);
-        mfma_rows(R4{}, af0, bf0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                if constexpr (FIRST)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf0[j], af0[i], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf0[j], af0[i], acc[i][j], 0, 0, 0);
+            }
         if constexpr (NJ == 8) w4_interleave<16, 3, 16>();    // 64 MFMAs | 16 reads
         else w4_interleave<12, 2, 8>();                       // 32 MFMAs | 12 reads
         __builtin_amdgcn_s_setprio(0);
@@ -355,7 +349,11 @@ __global__ void __launch_bounds__(256) gemm_w4_kernel(const GemmParams p) {
         mA[1] = mA[2];
         mB[1] = mB[2];
         ++s;
-      }
+    };
+
+    for (;;) {                                            // items
+        k_tile(std::true_type{});
+        for (int c_kt = 1; c_kt < c_nk; ++c_kt) k_tile(std::false_type{});
 
         // ================================================= item epilogue
         {
@@ -432,16 +430,20 @@ int gemm_w4(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t st
     if (p.ldc % 8 != 0 || p.strideC % 8 != 0 || (uintptr_t)p.C % 16 != 0) return -1;
     if (p.bias && (uintptr_t)p.bias % 16 != 0) return -1;
     if (p.lda % 8 != 0 || p.ldb % 8 != 0) return -1;
-    // GEMM_W4=1, the measured route: the deep-K data gradient only (profiles/w4_gemm_bench.txt, us,
-    // slowest / fastest of 5 interleaved repetitions, ping-pong -> this engine):
-    //   dx L2   32000 x 1024 x 4096   234.8-239.8 -> 230.1-233.4   won
-    //   proj L2 32000 x 4096 x 1024   266.5-330.9 -> 252.0-278.2   ranges overlap
-    //   proj L1 32000 x 4096 x 256     96.9-111.8 ->  97.3-121.8   equal
-    //   dx L1   32000 x 256 x 4096     77.0-80.2  -> 107.8-114.7   slower (125 items on 256 CUs; NT engine)
-    // and on the 256 x 128 tile (profiles/w4conv_gemm_bench.txt, NT engine -> this engine):
-    //   dx L1   32000 x 256 x 4096     80.8-82.7  ->  91.9-93.6    slower (250 items): not routed
+    // GEMM_W4=1, the measured routes: K >= 1024 and N >= 256 -- both data gradients and the layer-2
+    // projection (profiles/w4acc_gemm_bench.txt, us, fastest-slowest of 5 interleaved repetitions,
+    // ping-pong / NT ring -> this engine; a shape is won if this engine's slowest repetition beats
+    // the other's fastest):
+    //   dx L2     32000 x 1024 x 4096   231.0-238.4 -> 209.0-219.2   won
+    //   proj L2   32000 x 4096 x 1024   260.5-318.8 -> 227.6-253.5   won
+    //   dx L1     32000 x 256 x 4096     80.8-83.2  ->  71.6-72.5    won (256 x 128 tile, 250 items; NT ring)
+    //   proj L1   32000 x 4096 x 256     96.0-109.4 ->  87.7-97.5    ranges overlap: not routed
+    //   logits dx 32000 x 1024 x 96      21.7-21.9  ->  21.1-21.2    won by 0.5 us, short K: not routed
+    // (before the K loops accumulated in place -- profiles/w4acc_isa.txt -- proj L2 overlapped,
+    // 266.5-330.9 -> 252.0-278.2, and dx L1 lost, 80.8-82.7 -> 91.9-93.6: profiles/w4_gemm_bench.txt,
+    // w4conv_gemm_bench.txt)
     // 2: every covered shape
-    if (mode == 1 && (p.K < 2048 || p.N < 512)) return -1;
+    if (mode == 1 && (p.K < 1024 || p.N < 256)) return -1;
     const int ncu = cu_count();
     // the 256 x 128 tile where 256 x 256 items would cover at most half of the CUs (one round
     // either way, of items half as long)

@@ -169,7 +169,8 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
         const int k0 = kbeg + kt * BK;
         if constexpr (IM) {
             const int b = i >> 1, h = i & 1;
-            const bool ok = on && k0 + krow[h] < kend && (pmask[h] & t_bit[b]) != 0;
+            // (& not &&: a select among the MFMAs, never a branch on the lane's mask)
+            const bool ok = on & (k0 + krow[h] < kend) & ((pmask[h] & t_bit[b]) != 0);
             const unsigned base = (unsigned)(k0 * p.convC * 2) + t_sh[b];
             w4t_dma16(ra, buf + b * BLK + (h * 4 + wave) * 1024, ok ? va[h] + base : W4T_OOB, 0u);
             return;
@@ -203,10 +204,6 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
     };
 
     floatx4 acc[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
     bf16x8 af0[8], bf0[8], af1[8], bf1[8];                // fragments of kk = 0 / kk = 1
 
     // ---- prologue: K-tiles 0 and 1; tile 0 landed, its kk = 0 fragments read
@@ -225,7 +222,10 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) bf0[j] = frag_b(smem, j, 0);
 
-    for (int kt = 0; kt < nk; ++kt) {
+    // one K-tile. FIRST: the item's first K-tile, whose K0 MFMAs take the literal 0 as C
+    // (fma(a, b, +0) is what a zeroed accumulator computed): no zeroing pass
+    auto k_tile = [&](auto FIRST_, int kt) {
+        constexpr bool FIRST = decltype(FIRST_)::value;
         const char* cur = smem + (kt & 1) * BUF;
         const char* nxt = smem + ((kt + 1) & 1) * BUF;
         const unsigned curl = lds0 + (kt & 1) * BUF;
@@ -240,8 +240,11 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf0[j], af0[i], acc[i][j], 0, 0, 0);
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (FIRST)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf0[j], af0[i], floatx4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+                else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf0[j], af0[i], acc[i][j], 0, 0, 0);
+            }
 #pragma unroll
         for (int r = 0; r < 24; ++r) {                    // 24 x {2 MFMAs, 1 read}, 8 x {1, 1}, 8 MFMAs
             __builtin_amdgcn_sched_group_barrier(0x8, 2, 0);
@@ -289,7 +292,9 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
         }
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
-    }
+    };
+    k_tile(std::true_type{}, 0);
+    for (int kt = 1; kt < nk; ++kt) k_tile(std::false_type{}, kt);
     vm_wait<0>();                                         // the zero-fill pieces past the last K-tile
 
     // ---- epilogue: lane holds C[m][n .. n+3], m = m0 + wm*128 + i*16 + i16,
@@ -346,7 +351,9 @@ int gemm_w4tn(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t 
     // dW_h 512 x 2048 91.8-102.5 -> 77.2-84.3, L1 dW_x 256 x 2048 57.9-60.7 -> 51.1-52.6;
     // and each im2col conv weight gradient at B = 256 (profiles/w4conv_gemm_bench.txt, us per call
     // incl. the split-K reduce): conv7 1152 x 256 x 96000 113.3-120.0 -> 80.2-83.8,
-    // conv8 2304 x 256 x 96000 185.5-199.3 -> 125.2-132.2
+    // conv8 2304 x 256 x 96000 185.5-199.3 -> 125.2-132.2; with the im2col K loop accumulating in
+    // place (profiles/w4acc_isa.txt, w4acc_gemm_bench.txt) conv7 112.6-122.3 -> 76.3-80.9,
+    // conv8 184.8-200.6 -> 117.2-125.0, the recurrent gradients unchanged
     constexpr int LDS = 2 * 8 * 64 * 128;
     static DeviceOnce configured[2];
     const void* kern = im ? reinterpret_cast<const void*>(&gemm_w4tn_kernel<A_IM2COL_T>)

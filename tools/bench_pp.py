@@ -8,6 +8,8 @@ tests/).
     python tools/bench_pp.py --ab [reps]     # the plain GEMMs, GEMM_W4=0 against GEMM_W4=2 (the
                                              # one-wave-per-SIMD engine, csrc/gemm_w4.hip): interleaved in
                                              # this process, `reps` (5) repetitions of 20 launches each
+    python tools/bench_pp.py --ab 5 --parent LIB   # and a third engine beside them: GEMM_W4=2 of another
+                                             # commit's libocrk.so (tools/second_lib.py)
 """
 import os
 import sys
@@ -47,6 +49,8 @@ def ab_w4(reps):
     """Old and new engine interleaved; a shape is won if the new engine's slowest repetition beats
     the old engine's fastest."""
     from cnn_lstm_ctc_ocr_amd import options
+    import second_lib
+    var = second_lib.variants(second_lib.parent_from_argv())
     torch.manual_seed(0)
     dev = torch.device("cuda")
     bf = torch.bfloat16
@@ -56,25 +60,25 @@ def ab_w4(reps):
         w = ((torch.rand(N, Kd, device=dev) * 2 - 1) * 0.05).to(bf)
         bias = torch.randn(N, device=dev) if "proj" in tag else None
         f = lambda: K.gemm(a, w, trans_b=True, bias=bias, out_dtype=bf)  # noqa: E731
-        t = {0: [], 2: []}
+        t = {name: [] for name, _, _ in var}
         outs = {}
         for _ in range(reps):
-            for mode in (0, 2):
-                with options.override(GEMM_W4=mode):
-                    outs[mode] = f()
-                    t[mode].append(timed(f) * 1e3)
-        same = torch.equal(outs[0], outs[2])
-        for mode, name in ((0, "old"), (2, "w4")):
-            v = t[mode]
+            for name, handle, mode in var:
+                with second_lib.use(handle), options.override(GEMM_W4=mode):
+                    outs[name] = f()
+                    t[name].append(timed(f) * 1e3)
+        same = all(torch.equal(outs["old"], o) for o in outs.values())
+        for name, _, _ in var:
+            v = t[name]
             print(f"{tag:12s} {name:8s} {min(v):9.1f} {max(v):9.1f} {2.0 * M * N * Kd / min(v) / 1e6:14.1f}   "
                   + " ".join(f"{x:.1f}" for x in v))
-        print(f"{tag:12s} {'won' if max(t[2]) < min(t[0]) else 'not won'}; bit-identical: {same}", flush=True)
+        print(f"{tag:12s} {'won' if max(t['w4']) < min(t['old']) else 'not won'}; bit-identical: {same}", flush=True)
 
 
 def main():
     if "--ab" in sys.argv:
         i = sys.argv.index("--ab")
-        return ab_w4(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 5)
+        return ab_w4(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 and sys.argv[i + 1].isdigit() else 5)
     only = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else None
     torch.manual_seed(0)
     dev = torch.device("cuda")

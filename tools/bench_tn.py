@@ -3,6 +3,7 @@ the engine the dispatcher picks (OCRK_GEMM_PPTN=0: the 4-wave engine).
 
     python tools/bench_tn.py --ab [reps]   # GEMM_W4=0 against GEMM_W4=2 (the one-wave-per-SIMD engine,
                                            # csrc/gemm_w4tn.hip), interleaved, `reps` (5) repetitions each
+    python tools/bench_tn.py --ab 5 --parent LIB   # and GEMM_W4=2 of another commit's libocrk.so beside them
 """
 import os
 import sys
@@ -35,34 +36,36 @@ def ab_w4(reps):
     """Old and new engine interleaved (split-K reduce included in both); a shape is won if the new
     engine's slowest repetition beats the old engine's fastest."""
     from cnn_lstm_ctc_ocr_amd import options
+    import second_lib
+    var = second_lib.variants(second_lib.parent_from_argv())
     print(f"{'shape':20s} {'engine':6s} {'min us':>9s} {'max us':>9s} {'TFLOP/s (min)':>14s}   repetitions (us)")
     for n_in, N, ldb, tag in SHAPES:
         x = (torch.rand(R, n_in, device=dev) * 2 - 1).bfloat16()
         dG = (torch.rand(R, ldb, device=dev) * 2 - 1).bfloat16()
         sp = _splits(n_in, N, R)
-        t = {0: [], 2: []}
+        t = {name: [] for name, _, _ in var}
         outs = {}
         for _ in range(reps):
-            for mode in (0, 2):
-                with options.override(GEMM_W4=mode):
+            for name, handle, mode in var:
+                with second_lib.use(handle), options.override(GEMM_W4=mode):
                     gk = torch.zeros(n_in, N, device=dev)
                     f = lambda: K.gemm(x, dG, trans_a=True, out=gk, accumulate=True, M=n_in, N=N, K=R,  # noqa: E731
                                        lda=n_in, ldb=ldb, ldc=N, splits=sp)
                     f()
-                    outs[mode] = gk.clone()
-                    t[mode].append(_timed(f) * 1e3)
-        same = torch.equal(outs[0], outs[2])
-        for mode, name in ((0, "old"), (2, "w4")):
-            v = t[mode]
+                    outs[name] = gk.clone()
+                    t[name].append(_timed(f) * 1e3)
+        same = all(torch.equal(outs["old"], o) for o in outs.values())
+        for name, _, _ in var:
+            v = t[name]
             print(f"{tag:20s} {name:6s} {min(v):9.1f} {max(v):9.1f} {2.0 * n_in * N * R / min(v) / 1e6:14.1f}   "
                   + " ".join(f"{q:.1f}" for q in v))
-        print(f"{tag:20s} splits {sp}: {'won' if max(t[2]) < min(t[0]) else 'not won'}; bit-identical: {same}",
+        print(f"{tag:20s} splits {sp}: {'won' if max(t['w4']) < min(t['old']) else 'not won'}; bit-identical: {same}",
               flush=True)
 
 
 if "--ab" in sys.argv:
     _i = sys.argv.index("--ab")
-    ab_w4(int(sys.argv[_i + 1]) if len(sys.argv) > _i + 1 else 5)
+    ab_w4(int(sys.argv[_i + 1]) if len(sys.argv) > _i + 1 and sys.argv[_i + 1].isdigit() else 5)
     sys.exit(0)
 
 tot = 0.0

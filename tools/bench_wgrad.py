@@ -6,6 +6,7 @@ row-walking, 4-wave TN, ping-pong / one-wave-per-SIMD TN im2col) and TFLOP/s.
     python tools/bench_wgrad.py --ab [reps]  # conv7 / conv8, GEMM_W4=0 (gemm_pptn) against GEMM_W4=2
                                              # (gemm_w4tn), interleaved in this process, `reps` (5)
                                              # repetitions of 20 calls each, incl. the split-K reduce
+    python tools/bench_wgrad.py --ab 5 --parent LIB   # and GEMM_W4=2 of another commit's libocrk.so beside them
 """
 import os
 import sys
@@ -39,30 +40,33 @@ def ab_w4(reps):
     """Old and new engine interleaved; a layer is won if the new engine's slowest repetition beats
     the old engine's fastest."""
     from cnn_lstm_ctc_ocr_amd import options
+    import second_lib
+    var = second_lib.variants(second_lib.parent_from_argv())
     for name, H, W, cin, cout in LAYERS[5:]:
         x = (torch.rand(B, H, W, cin, device=dev) * 2 - 1).bfloat16()
         dy = (torch.rand(B, H, W, cout, device=dev) * 2 - 1).bfloat16()
         dw = torch.zeros(9 * cin, cout, device=dev)
         f = lambda: K.conv3x3_bwd_weight(x, dy, dw, accumulate=False)  # noqa: E731
-        t = {0: [], 2: []}
+        t = {n: [] for n, _, _ in var}
         outs = {}
         for _ in range(reps):
-            for mode in (0, 2):
-                with options.override(GEMM_W4=mode):
-                    t[mode].append(timed(f, 3, 20))
-                    outs[mode] = dw.clone()
+            for n, handle, mode in var:
+                with second_lib.use(handle), options.override(GEMM_W4=mode):
+                    t[n].append(timed(f, 3, 20))
+                    outs[n] = dw.clone()
         fl = 2.0 * B * H * W * 9 * cin * cout
-        for mode in (0, 2):
-            v = t[mode]
-            print(f"{name} {cin}->{cout} GEMM_W4={mode}: " + " ".join(f"{u:6.1f}" for u in v) +
+        for n, _, mode in var:
+            v = t[n]
+            print(f"{name} {cin}->{cout} {n:6s} GEMM_W4={mode}: " + " ".join(f"{u:6.1f}" for u in v) +
                   f"  us   fastest {min(v):6.1f} slowest {max(v):6.1f}  {fl / min(v) / 1e6:6.1f} TFLOP/s at fastest")
-        print(f"{name}: bitwise equal {bool(torch.equal(outs[0], outs[2]))}; won {max(t[2]) < min(t[0])}", flush=True)
+        same = all(torch.equal(outs["old"], o) for o in outs.values())
+        print(f"{name}: bitwise equal {same}; won {max(t['w4']) < min(t['old'])}", flush=True)
 
 
 def main():
     if "--ab" in sys.argv:
         i = sys.argv.index("--ab")
-        return ab_w4(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 5)
+        return ab_w4(int(sys.argv[i + 1]) if len(sys.argv) > i + 1 and sys.argv[i + 1].isdigit() else 5)
     for name, H, W, cin, cout in LAYERS:
         x = (torch.rand(B, H, W, cin, device=dev) * 2 - 1).bfloat16()
         dy = (torch.rand(B, H, W, cout, device=dev) * 2 - 1).bfloat16()
