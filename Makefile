@@ -32,8 +32,9 @@ build/%.o: $(CSRC)/%.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# tools-only build: experiment toggles + diagnostics (include/ocrk_debug.h);
-# tools load it with OCRK_LIB=tools/libocrk_exp.so. Never the product library.
+# tools-only build: the instruments (include/ocrk_debug.h: the LSTM debug stamps,
+# and the NT tile sweep OCRK_GEMM_NT_CFG); tools load it with
+# OCRK_LIB=tools/libocrk_exp.so. Never the product library.
 EXPOBJ := $(patsubst $(CSRC)/%.hip,build/exp/%.o,$(SRC))
 EXPLIB := tools/libocrk_exp.so
 

@@ -224,14 +224,6 @@ def raise_for_status(word):
 # include/ocrk_debug.h (exported only by tools/libocrk_exp.so, `make exp`)
 DEBUG_SIGNATURES = {
     "ocrk_lstm_debug_stamps": [_p],
-    # routes measured slower and kept out of the product library (round 6)
-    "ocrk_conv2_bwd_weight_c1x_supported": [_i32, _i32, _i32, _i32],
-    "ocrk_conv2_bwd_weight_c1x": [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p, _sz, _i32, _p],
-    "ocrk_stream_wait": [_p, _p, _i32],
-    "ocrk_stream_create_cu_limited": [_i32, _p],
-    "ocrk_stream_destroy": [_p],
-    "ocrk_lstm_fwd_persistent_x_supported": [_i32, _i32, _i32],
-    "ocrk_lstm_fwd_persistent_x": [_p, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
 }
 
 _lib = None

@@ -24,7 +24,6 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // set up thread-safely: one process may drive several GPUs, one thread each
 // ("a per-device kernel-module cache (thread-safe)").
 constexpr int kMaxDevices = 64;
-constexpr int kMaxCuWords = 32;                       // CU-mask words (1024 CUs)
 inline int current_device() {
     int d = 0;
     (void)hipGetDevice(&d);
@@ -69,12 +68,9 @@ enum Option : int {
     OPT_CONV_WGRAD_BLOCKS,    // 1 (default) conv5/6 weight gradients as channel blocks, 2 conv7/8 too, 0 TN
     OPT_LSTM_SPIN_LIMIT,      // polls before a persistent hand-off wait gives up (<= 0: 1 << 22)
     OPT_PERSIST_LATE,         // 1 (default) late epilogue loads behind the staging DMA, 0 at the step top
-    OPT_LSTM_BWD_KSPLIT,      // 1: the K-split persistent BPTT (opt-in)
-    OPT_LSTM_BWD_PB16,        // 1: K-split partial products exchanged in bf16
     OPT_LSTM_BWD_R16,         // 1 (default) 16-row / 64-unit BPTT members at H = 512, 0 the 32-row gather
     OPT_CTC_LDS,              // 1 (default) CTC lattices in LDS when they fit, 0 in the global workspace
     OPT_PP_PERSIST_NK,        // ping-pong GEMM: persistent workgroups when K-tiles per item <= this (8)
-    OPT_PP_DEEP,              // 1: the deep-lead ping-pong schedule for the plain (A_ROWK) GEMMs
     OPT_NT_F32_EXACT,         // 1 (default): exact-mode fp32 convolutions on the NT ring (0: generic engine)
     OPT_NT_F32_MASK,          // 1 (default): the masked fp32 data gradients on the NT ring too (0: generic engine)
     OPT_NT_F32_X6,            // 1: exact-mode NT convolutions as six bf16 products (fp32-precision split; opt-in)

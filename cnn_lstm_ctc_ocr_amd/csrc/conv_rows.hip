@@ -185,14 +185,9 @@ __device__ __forceinline__ void c1_make_row(char* slot, const float* ximg, int r
     }
 }
 
-// C1X (1: u8, 2: bf16 image): conv2's x = y1 is not read but recomputed per row from the
-// image (c1_make_row: the same bits conv12_fwd_rows_kernel produced), so the fused forward
-// need not write y1 at all -- 125 MB written and 125 MB read less per step at C3
-template <int C1X = 0>
 __global__ void __launch_bounds__(256, 1)
 conv3x3_wgrad_rows_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy, float* __restrict__ part,
-                          int B, int H, int W, const void* __restrict__ img = nullptr,
-                          const float* __restrict__ w1 = nullptr, const float* __restrict__ b1 = nullptr) {
+                          int B, int H, int W) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -202,21 +197,6 @@ conv3x3_wgrad_rows_kernel(const bf16* __restrict__ x, const bf16* __restrict__ d
 
     // zero both rings once: the pad pixels (x rows 0 and W+1.., dy rows W..255) stay zero
     for (int i = tid; i < RW_RING / 16; i += 256) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
-    float* ximg = reinterpret_cast<float*>(smem + RW_LDS);           // C1X: [8][RD_XROW] image rows
-    if constexpr (C1X != 0)
-        for (int i = tid; i < C12_XSLOTS * RD_XROW; i += 256) ximg[i] = 0.f;
-    C1Frags f1;
-    if constexpr (C1X != 0) c1_frags(f1, w1, b1, i16, g);
-    const int XW = W + 2;
-    unsigned xraw = 0;
-    auto x_fetch = [&](int bb, int r) {
-        const size_t o = ((size_t)bb * (H + 2) + min(max(r, 0), H + 1)) * XW + min(tid, XW - 1);
-        if constexpr (C1X == 1) xraw = reinterpret_cast<const uint8_t*>(img)[o];
-        else if constexpr (C1X == 2) xraw = reinterpret_cast<const unsigned short*>(img)[o];
-    };
-    auto x_put = [&](int r) {
-        if (tid < XW) ximg[(r & (C12_XSLOTS - 1)) * RD_XROW + tid] = C1X == 1 ? conv1_pre_u8(xraw) : __uint_as_float(xraw << 16);
-    };
 
     floatx4 acc[9][2][2];
 #pragma unroll
@@ -261,31 +241,17 @@ conv3x3_wgrad_rows_kernel(const bf16* __restrict__ x, const bf16* __restrict__ d
         auto xrow = [&](int r) { return xb + (size_t)r * W * RW_CI; };
         auto drow = [&](int r) { return db + (size_t)r * W * RW_CO; };
         __syncthreads();                            // the previous image's last reads are done
-        if constexpr (C1X != 0) {
-            // prologue: image rows 0 .. 4 into the image ring, then x rows 0, 1 produced
-            for (int r = 0; r <= 4 && r < H + 2; ++r) {
-                x_fetch(b, r);
-                x_put(r);
-            }
-            __syncthreads();
-            c1_make_row<C1X>(smem + xslot(0), ximg, 0, W, wave, i16, g, f1, nullptr, nullptr);
-            if (H > 1) c1_make_row<C1X>(smem + xslot(1), ximg, 1, W, wave, i16, g, f1, nullptr, nullptr);
-            load_row(drow(0), sd[1]);
-            store_row(dslot(0), 0, sd[1]);
-            if (H > 1) load_row(drow(1), sd[0]);
-        } else {
-            // prologue: x rows 0, 1 and dy row 0 into the ring; x row 2 / dy row 1 into set 0
-            load_row(xrow(0), sx[1]);
-            load_row(drow(0), sd[1]);
-            store_row(xslot(0), 1, sx[1]);
-            store_row(dslot(0), 0, sd[1]);
-            if (H > 1) {
-                load_row(xrow(1), sx[1]);
-                store_row(xslot(1), 1, sx[1]);
-                load_row(drow(1), sd[0]);
-            }
-            if (H > 2) load_row(xrow(2), sx[0]);
+        // prologue: x rows 0, 1 and dy row 0 into the ring; x row 2 / dy row 1 into set 0
+        load_row(xrow(0), sx[1]);
+        load_row(drow(0), sd[1]);
+        store_row(xslot(0), 1, sx[1]);
+        store_row(dslot(0), 0, sd[1]);
+        if (H > 1) {
+            load_row(xrow(1), sx[1]);
+            store_row(xslot(1), 1, sx[1]);
+            load_row(drow(1), sd[0]);
         }
+        if (H > 2) load_row(xrow(2), sx[0]);
         // step h: rows h-1..h+1 of x and row h of dy are in the ring; set P holds
         // x row h+2 / dy row h+1 (loaded during step h-1); set 1-P receives x row
         // h+3 / dy row h+2 now
@@ -294,8 +260,7 @@ conv3x3_wgrad_rows_kernel(const bf16* __restrict__ x, const bf16* __restrict__ d
             __syncthreads();
             // unconditional (a clamped row past the image): a fixed count of loads in
             // flight lets the stores below wait for the older set only
-            if constexpr (C1X != 0) x_fetch(b, h + 5);
-            else load_row(xrow(min(h + 3, H - 1)), sx[1 - P]);
+            load_row(xrow(min(h + 3, H - 1)), sx[1 - P]);
             load_row(drow(min(h + 2, H - 1)), sd[1 - P]);
             const char* dsl = smem + dslot(h);
 #pragma unroll
@@ -331,13 +296,7 @@ conv3x3_wgrad_rows_kernel(const bf16* __restrict__ x, const bf16* __restrict__ d
                 }
             }
             // rows h+2 / h+1 into the slots nobody reads this step (x row h-2's, dy row h-1's)
-            if constexpr (C1X != 0) {
-                // x row h+2 produced from image rows h+2 .. h+4; image row h+5 into the slot of h-3
-                if (h + 2 < H) c1_make_row<C1X>(smem + xslot(h + 2), ximg, h + 2, W, wave, i16, g, f1, nullptr, nullptr);
-                if (h + 5 < H + 2) x_put(h + 5);
-            } else {
-                if (h + 2 < H) store_row(xslot(h + 2), 1, sx[P]);
-            }
+            if (h + 2 < H) store_row(xslot(h + 2), 1, sx[P]);
             if (h + 1 < H) store_row(dslot(h + 1), 0, sd[P]);
         };
         for (int h = 0; h < H; h += 2) {
@@ -2027,37 +1986,6 @@ int conv_rows_dgrad_bits(const void* dy, int B, int H, int W, int cout, const vo
     return launch_dgrad_co<64, 64, 128, 1, true>(dy, B, H, W, w_bwd, dx, bits, stats, s);
 }
 
-#ifdef OCRK_EXPERIMENTS
-// conv2's weight gradient with conv1's output recomputed from the image (no y1 tensor):
-// dw [3][3][32][32] (+)= sum y1 (x) dz, y1 = relu(conv1(img)) produced per row by
-// c1_make_row -- the bits conv12_fwd_rows_kernel made in the forward
-constexpr int RW_LDS_C1X = RW_LDS + C12_XSLOTS * RD_XROW * 4;     // 155.6 KB (one workgroup per CU)
-
-int conv_rows_wgrad_c1x(const void* img, int x_is_u8, const float* w1, const float* b1, const void* dy, int B, int H,
-                        int W, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t s) {
-    if (!rows_enabled() || W < 1 || H < 1 || B < 1 || W > RW_MAXW) return -1;
-    if (ws_bytes < conv_rows_wgrad_ws_bytes(B, RW_CI, RW_CO) || (uintptr_t)ws % 16 != 0) return -1;
-    const int grid = std::min(B, std::max(cu_count(), 1));
-    static DeviceOnce cfg_u8, cfg_bf;
-    if (x_is_u8) {
-        set_dyn_lds(cfg_u8, reinterpret_cast<const void*>(&conv3x3_wgrad_rows_kernel<1>), RW_LDS_C1X);
-        conv3x3_wgrad_rows_kernel<1><<<grid, 256, RW_LDS_C1X, s>>>(nullptr, (const bf16*)dy, (float*)ws, B, H, W, img,
-                                                                   w1, b1);
-    } else {
-        set_dyn_lds(cfg_bf, reinterpret_cast<const void*>(&conv3x3_wgrad_rows_kernel<2>), RW_LDS_C1X);
-        conv3x3_wgrad_rows_kernel<2><<<grid, 256, RW_LDS_C1X, s>>>(nullptr, (const bf16*)dy, (float*)ws, B, H, W, img,
-                                                                   w1, b1);
-    }
-    int st = launch_status("conv3x3_wgrad_rows_c1x");
-    if (st) return st;
-    GemmParams p = {};
-    p.M = 9 * RW_CI; p.N = RW_CO; p.K = B * H * W; p.batch = 1;
-    p.C = dw; p.ldc = RW_CO; p.c_bf16 = 0; p.accumulate = accumulate; p.alpha = 1.f;
-    p.splits = grid; p.splitk_ws = (float*)ws;
-    return splitk_finish(p, s);
-}
-#endif  // OCRK_EXPERIMENTS
-
 bool conv12_fwd_covers(int B, int H, int W) {
     return rows_enabled() && B >= 1 && H >= 1 && W >= 1 && W <= RW_MAXW;
 }
@@ -2200,8 +2128,8 @@ int conv_rows_wgrad(const void* x, const void* dy, int B, int H, int W, int cin,
     if (cin != RW_CI || cout != RW_CO || W > RW_MAXW) return -1;
     const int grid = std::max(2, std::min(B, std::max(cu_count(), 1)));   // (>= 2: as launch_rows_co)
     static DeviceOnce cfg;
-    set_dyn_lds(cfg, reinterpret_cast<const void*>(&conv3x3_wgrad_rows_kernel<0>), RW_LDS);
-    conv3x3_wgrad_rows_kernel<0><<<grid, 256, RW_LDS, s>>>((const bf16*)x, (const bf16*)dy, (float*)ws, B, H, W);
+    set_dyn_lds(cfg, reinterpret_cast<const void*>(&conv3x3_wgrad_rows_kernel), RW_LDS);
+    conv3x3_wgrad_rows_kernel<<<grid, 256, RW_LDS, s>>>((const bf16*)x, (const bf16*)dy, (float*)ws, B, H, W);
     int st = launch_status("conv3x3_wgrad_rows");
     if (st) return st;
     GemmParams p = {};

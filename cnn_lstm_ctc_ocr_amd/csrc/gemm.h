@@ -85,8 +85,9 @@ int gemm_nt(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t st
 bool f32_exact_mfma();
 
 // 8-wave ping-pong engine (gemm_pp.hip): 256 x {256,128} x 64 tiles for the
-// large bf16 A_ROWK / A_IM2COL / A_IM2COL_FLIP x B_NK GEMMs (N >= 96). Returns
-// -1 when it does not cover the call. OCRK_GEMM_PP=0 disables it.
+// large plain bf16 A_ROWK x B_NK GEMMs (bf16 C, bias / ReLU epilogue, no mask
+// or stats, N >= PP_MIN_N). Returns -1 when it does not cover the call.
+// OCRK_GEMM_PP=0 disables it.
 int gemm_pp(const GemmParams& p, int amode, int bmode, int dtype, hipStream_t stream);
 
 // One-wave-per-SIMD 256 x 256 x 64 engines (4 waves, a 128 x 128 register tile each): gemm_w4

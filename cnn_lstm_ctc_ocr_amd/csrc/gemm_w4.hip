@@ -81,16 +81,6 @@ namespace ocrk {
 
 namespace {
 
-constexpr unsigned W4_OOB = 0x80000000u;
-
-__device__ __forceinline__ void w4_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
 // NR x {NM MFMAs, 1 LDS read}, then the cluster's remaining MFMAs
 template <int NR, int NM, int REST>
 __device__ __forceinline__ void w4_interleave() {
@@ -110,12 +100,6 @@ typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ i32x4_t w4_rsrc(const void* base, int bytes) {
     const uint64_t b = (uint64_t)base;
     return i32x4_t{(int)(unsigned)b, (int)((unsigned)(b >> 32) & 0xffffu), bytes, 0x00020000};
-}
-
-// lds_dma16_asm with the LDS byte address as a number and a scalar byte offset (soffset)
-__device__ __forceinline__ void w4_dma16(const i32x4_t& r, unsigned lds, unsigned voff, unsigned soff) {
-    asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 :: "v"(voff), "s"(r), "s"(soff), "{m0}"(lds) : "memory");
 }
 
 // BN = 256: the geometry above. BN = 128, for calls whose 256 x 256 items would leave half of the

@@ -50,22 +50,6 @@ namespace ocrk {
 
 namespace {
 
-constexpr unsigned W4T_OOB = 0x80000000u;
-
-__device__ __forceinline__ void w4t_barrier() {
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-
-// lds_dma16_asm with the LDS byte address as a number and a scalar byte offset (soffset)
-__device__ __forceinline__ void w4t_dma16(const i32x4_t& r, unsigned lds, unsigned voff, unsigned soff) {
-    asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-                 :: "v"(voff), "s"(r), "s"(soff), "{m0}"(lds) : "memory");
-}
-
 template <int AM>
 __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
     constexpr bool IM = AM == A_IM2COL_T;
@@ -172,18 +156,18 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
             // (& not &&: a select among the MFMAs, never a branch on the lane's mask)
             const bool ok = on & (k0 + krow[h] < kend) & ((pmask[h] & t_bit[b]) != 0);
             const unsigned base = (unsigned)(k0 * p.convC * 2) + t_sh[b];
-            w4t_dma16(ra, buf + b * BLK + (h * 4 + wave) * 1024, ok ? va[h] + base : W4T_OOB, 0u);
+            w4_dma16(ra, buf + b * BLK + (h * 4 + wave) * 1024, ok ? va[h] + base : W4_OOB, 0u);
             return;
         }
         const bool ok = on && k0 + krow[i & 1] < kend && m0 + 64 * (i >> 1) + 8 * chunk < p.M;
         const unsigned soff = on ? (unsigned)(k0 * (int)p.lda * 2 + 128 * (i >> 1)) : 0u;
-        w4t_dma16(ra, buf + (i >> 1) * BLK + ((i & 1) * 4 + wave) * 1024, ok ? va[i & 1] : W4T_OOB, soff);
+        w4_dma16(ra, buf + (i >> 1) * BLK + ((i & 1) * 4 + wave) * 1024, ok ? va[i & 1] : W4_OOB, soff);
     };
     auto dma_b = [&](int i, int kt, unsigned buf, bool on) {
         const int k0 = kbeg + kt * BK;
         const bool ok = on && k0 + krow[i & 1] < kend && n0 + 64 * (i >> 1) + 8 * chunk < p.N;
         const unsigned soff = on ? (unsigned)(k0 * (int)p.ldb * 2 + 128 * (i >> 1)) : 0u;
-        w4t_dma16(rb, buf + A_BYTES + (i >> 1) * BLK + ((i & 1) * 4 + wave) * 1024, ok ? vb[i & 1] : W4T_OOB, soff);
+        w4_dma16(rb, buf + A_BYTES + (i >> 1) * BLK + ((i & 1) * 4 + wave) * 1024, ok ? vb[i & 1] : W4_OOB, soff);
     };
 
     // ---- transposed fragment reads (frag_tr): lane reads k-row kr0 (+16) of the 32-deep k-block,
@@ -216,7 +200,7 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
         for (int i = 0; i < NU; ++i) dma_b(i, t2, lds0 + t2 * BUF, t2 < nk);
     }
     vm_wait<2 * NU>();
-    w4t_barrier();
+    w4_barrier();
 #pragma unroll
     for (int i = 0; i < 8; ++i) af0[i] = frag_a(smem, i, 0);
 #pragma unroll
@@ -261,7 +245,7 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         vm_wait<NU>();
-        w4t_barrier();
+        w4_barrier();
         // ---- K1a: kk = 1, acc rows 0-3 | A reads of K-tile kt+1 | UA(kt+2) into buffer kt & 1
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -277,7 +261,7 @@ __global__ void __launch_bounds__(256) gemm_w4tn_kernel(const GemmParams p) {
         __builtin_amdgcn_s_setprio(0);
         // ---- M: UB(kt+1) landed (UA(kt+2) stays in flight)
         vm_wait<NU>();
-        w4t_barrier();
+        w4_barrier();
         // ---- K1b: kk = 1, acc rows 4-7 | B reads of K-tile kt+1 | UB(kt+2)
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll

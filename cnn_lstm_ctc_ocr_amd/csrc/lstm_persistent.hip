@@ -78,37 +78,22 @@ static unsigned lstm_spin_limit() { return recur_spin_limit(); }
 // hand-off poll, behind the h_{s-1} LDS-DMA, and written to LDS after the MFMAs:
 // vmcnt is in-order, so gx loads issued before the poll made every poll (and
 // the staging wait) wait for their HBM latency as well.
-// NIN > 0 (H = 512, LATE; the first layer, In = NIN = 256): the input projection
-// x_t . W_x + b is FUSED into the loop instead of read as gx. The member's
-// W_x^T slice (its 128 gate columns x NIN) stays in registers like W_h's; the
-// 32 rows x_t of the step (each row's own t: reverse direction, ragged lengths)
-// are staged by LDS-DMA one step ahead into a 2-deep ring (16-B pieces
-// XOR-swizzled by row, so a fragment read of 16 rows hits 16 bank groups) --
-// issued right behind the h_{s-1} staging DMA, landed by that step's publish
-// drain; the x . W_x MFMAs of step s run at its top, before the hand-off poll
-// (they do not depend on h), the bias is added in the cell. No gx tensor: the
-// [T*B, 8H] projection GEMM and its 2 x 262 MB of HBM traffic (B = 256) go away.
-template <int KS, bool LATE = false, int NIN = 0>
+template <int KS, bool LATE = false>
 __global__ void __launch_bounds__(256, 1)
 lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__ whT, bf16* __restrict__ hx,
                            const int* __restrict__ seq_len, int T, int B, bf16* __restrict__ out,
                            bf16* __restrict__ hprev_t, float* __restrict__ cprev_t, bf16* __restrict__ acts_t,
                            unsigned* __restrict__ flags, unsigned* __restrict__ err, unsigned spin_limit,
-                           long long* __restrict__ dbg, const bf16* __restrict__ xin = nullptr,
-                           const bf16* __restrict__ wxT = nullptr, const float* __restrict__ bias = nullptr) {
+                           long long* __restrict__ dbg) {
     constexpr int H = KS * 32;
     constexpr int G4 = 4 * H;
     constexpr int NU = H / PHU;                         // members per group
     constexpr int LDH = H + 8;                          // padded LDS row (bf16 elements)
     static_assert(NU <= 64, "one poll lane per member");
     constexpr int LDG = 4 * PHU + 4;                    // padded gate row (floats)
-    constexpr bool fx = NIN > 0;
-    static_assert(!fx || (LATE && KS == 16 && NIN == 256), "fused input projection: H = 512, In = 256, late loads");
-    constexpr int KX = fx ? NIN / 32 : 1;               // k-steps of the input projection
     __shared__ __attribute__((aligned(16))) unsigned short sh[PBR * LDH];
-    __shared__ __attribute__((aligned(16))) unsigned short sgx[fx ? 8 : PBR * 4 * PHU];   // [row][gate][unit] bf16
+    __shared__ __attribute__((aligned(16))) unsigned short sgx[PBR * 4 * PHU];   // [row][gate][unit] bf16
     __shared__ __attribute__((aligned(16))) float sG[PBR * LDG];                 // [row][gate][unit] f32
-    __shared__ __attribute__((aligned(16))) unsigned short sx[fx ? 2 * PBR * NIN : 8];    // x ring [2][row][NIN]
     __shared__ int s_len[PBR];
 
     int group, member;
@@ -138,22 +123,6 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" ::"v"(bw[j][ks]));   // see the BPTT kernel
 
-    // ---- fused input projection: resident W_x^T fragments (same N-tile / lane map as W_h)
-    bf16x8 bx[fx ? 2 : 1][KX];
-    if constexpr (fx) {
-        const bf16* xdir = wxT + (size_t)dir * G4 * NIN;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const bf16* row = xdir + (size_t)((2 * j + (c >> 3)) * H + my_unit) * NIN + 8 * g;
-#pragma unroll
-            for (int kx = 0; kx < KX; ++kx) bx[j][kx] = *reinterpret_cast<const bf16x8*>(row + kx * 32);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int kx = 0; kx < KX; ++kx) asm volatile("" ::"v"(bx[j][kx]));
-    }
-
     // ---- the epilogue item of this thread: row er, units eu..eu+3 (all 4 gates)
     const int er = tid >> 3, eu = 4 * (tid & 7);
     const int elen = seq_len[b0 + er];
@@ -162,49 +131,8 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
     // measured 2.74 -> 2.64 us/step forward, 3.51 -> 3.39 BPTT (the same below)
     asm volatile("" ::"v"(elen));
     float cst[4] = {0.f, 0.f, 0.f, 0.f}, hst[4] = {0.f, 0.f, 0.f, 0.f};
-    float bsr[fx ? 4 : 1][4];                           // fused: the projection bias of the thread's 16 gate columns
-    if constexpr (fx) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bsr[k][e] = bias[dir * G4 + k * H + u0 + eu + e];
-    }
     if (tid < PBR) s_len[tid] = seq_len[b0 + tid];
     __syncthreads();
-
-    // fused: x_t rows of step `step` into ring slot `buf` -- 4 LDS-DMA wave instructions
-    // of 2 rows x 512 B; lane l fetches logical piece (l & 31) ^ (row & 15) into slot l & 31
-    const __amdgpu_buffer_rsrc_t x_rsrc = uniform_rsrc(fx ? (const void*)xin : (const void*)whT,
-                                                       fx ? (int64_t)T * B * NIN * 2 : 16);
-    // the x rows this lane fetches (fixed over the steps): their lengths and fixed byte parts
-    int xlen[fx ? 4 : 1], xfix[fx ? 4 : 1];
-    if constexpr (fx) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int r = 2 * (w * 4 + q) + (lane >> 5);
-            xlen[q] = s_len[r];
-            xfix[q] = (b0 + r) * NIN * 2 + 16 * ((lane & 31) ^ (r & 15));
-        }
-    }
-    auto issue_x = [&](int step, int buf) {
-        if constexpr (fx) {
-            const int wu = __builtin_amdgcn_readfirstlane(w);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned off = step < T
-                    ? (unsigned)step_time(dir, step, xlen[q]) * (unsigned)(B * NIN * 2) + (unsigned)xfix[q]
-                    : 0x80000000u;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                    x_rsrc, (__attribute__((address_space(3))) void*)(sx + (buf * PBR + 2 * (wu * 4 + q)) * NIN), 16,
-                    off, 0, 0, 0);
-            }
-        }
-    };
-    if constexpr (fx) {
-        issue_x(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
 
     // gx tile loader: 32 rows x 4 gates x 4 chunks of 8 units = 512 16-B pieces, 2 per thread
     int gx_lr[2], gx_gate[2], gx_q[2];
@@ -248,25 +176,6 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[mt][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-        // fused: gates = x_t . W_x (independent of h) -- run in the shadow of the
-        // h_{s-1} staging DMA (at s = 0 there is none)
-        auto x_mma = [&]() {
-            if constexpr (fx) {
-                const unsigned short* xs = sx + (s & 1) * PBR * NIN;
-#pragma unroll
-                for (int kx = 0; kx < KX; ++kx) {
-                    const int sl = (4 * kx + g) ^ c;             // rows c and 16 + c share the swizzle
-                    const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&xs[c * NIN + 8 * sl]);
-                    const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&xs[(16 + c) * NIN + 8 * sl]);
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        acc[0][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bx[j][kx], acc[0][j], 0, 0, 0);
-                        acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bx[j][kx], acc[1][j], 0, 0, 0);
-                    }
-                }
-            }
-        };
-
         if (s > 0) {
             // 1. wait until every member of the group published h_{s-1} (flag >= s)
             if (w == 0) {
@@ -308,12 +217,7 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
                             (unsigned)((hbase + (int64_t)r * H) * 2) + lo, 0, 0, 16);
                     }
                 }
-                if constexpr (fx) {
-                    asm volatile("" ::: "memory");
-                    issue_x(s + 1, (s + 1) & 1);                 // next step's x rows behind the 8 DMAs
-                    x_mma();                                     // while the h rows land
-                    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                } else if constexpr (late) {
+                if constexpr (late) {
                     asm volatile("" ::: "memory");
                     load_gx();                                   // 2 loads behind the 8 DMAs
                     asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -336,9 +240,6 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
                 *reinterpret_cast<u32x4*>(&sh[row * LDH + 8 * kq]) = hv[v];
             }
             }
-        } else if constexpr (fx) {
-            issue_x(1, 1);
-            x_mma();
         } else if constexpr (late) {
             load_gx();
         }
@@ -363,7 +264,7 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
             }
         }
 
-        if constexpr (late && !fx) {
+        if constexpr (late) {
             // the gx tile, landed during the MFMAs (read after the barrier below; the
             // previous step's reads of sgx ended before its flag barrier)
 #pragma unroll
@@ -389,15 +290,10 @@ lstm_fwd_persistent_kernel(const bf16* __restrict__ gx, const bf16* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const f32x4 z = *reinterpret_cast<const f32x4*>(&sG[er * LDG + k * PHU + eu]);
-            if constexpr (fx) {
+            typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+            const u16x4 xg = *reinterpret_cast<const u16x4*>(&sgx[(er * 4 + k) * PHU + eu]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) a4[k][e] = z[e] + bsr[k][e];
-            } else {
-                typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-                const u16x4 xg = *reinterpret_cast<const u16x4*>(&sgx[(er * 4 + k) * PHU + eu]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a4[k][e] = z[e] + bits_f(xg[e]);
-            }
+            for (int e = 0; e < 4; ++e) a4[k][e] = z[e] + bits_f(xg[e]);
         }
         float hn[4], cp[4], hp[4];
 #pragma unroll
@@ -1141,264 +1037,6 @@ lstm_bwd_r16_kernel(const bf16* __restrict__ wh, bf16* __restrict__ dzx, const i
     }
 }
 
-// ---------------------------------------------------- backward, K-split form
-// The same BPTT with the recurrent product split over the members by K
-// instead of by output unit (opt-in, OCRK_LSTM_BWD_KSPLIT=1; the default is the
-// gather form above). Member m computes, from ITS OWN dz (the 4 gates x 32
-// units it just produced, never exchanged), the partial product
-//   P_m[32 rows, H units] = dz_m[32 rows, 128 gate cols] . W_h[H units, own 128 gate cols]^T
-// (K = 128: one 32-deep k-step per gate; wave w: units w H/4 .. +H/4, its W_h
-// slice resident in VGPRs as B fragments), and publishes it as NU f32 blocks
-// of 32 rows x 32 units, block m' for the member that owns those units. A
-// member's dh_rec is then the fixed-order sum of the NU blocks addressed to it
-// (one 16-B load per block per thread, all in flight at once, summed in
-// registers -- deterministic). Per step and member this moves 64 KB in and
-// 64 KB out (f32) instead of gathering every member's dz rows (128 KB bf16 in),
-// keeps no staged rows in LDS (8.5 KB instead of 149 KB), and takes dz out of
-// the exchange, so dh is formed from f32 partial sums of the UNROUNDED-in-
-// exchange products (dz enters the MFMA in bf16 as before).
-// Thread mapping of the cell's gradient = the MFMA output layout: wave w
-// handles M-tile w >> 1 and the 16-unit half w & 1 of the member's units;
-// lane (c, g) holds rows 16 (w >> 1) + 4 g + r (r = 0..3) of unit 16 (w & 1) + c.
-template <int KS, bool PB16>
-__global__ void __launch_bounds__(256, 1)
-lstm_bwd_ksplit_kernel(const bf16* __restrict__ wh, void* __restrict__ px, const int* __restrict__ seq_len, int T,
-                       int B, const bf16* __restrict__ dout, const float* __restrict__ cprev_t,
-                       const bf16* __restrict__ acts_t, bf16* __restrict__ dG_t, unsigned* __restrict__ flags,
-                       unsigned* __restrict__ err, unsigned spin_limit, long long* __restrict__ dbg,
-                       float* __restrict__ bpart) {
-    constexpr int H = KS * 32;
-    constexpr int G4 = 4 * H;
-    constexpr int NU = H / PHU;                          // members per group
-    constexpr int NT = H / 64;                           // 16-unit N-tiles per wave (H/4 units)
-    constexpr int LDA = 4 * PHU + 8;                     // padded dz row: 128 gate cols + 8 (bf16)
-    constexpr int BLK = PBR * PHU;                       // elements per (dst, src) block
-    constexpr int EB = PB16 ? 2 : 4;                     // bytes per exchanged element
-    static_assert(NU <= 64 && (H == 256 || H == 512), "one poll lane per member");
-    __shared__ __attribute__((aligned(16))) unsigned short sA[PBR * LDA];
-    // the step's epilogue operands, staged row-wise (vector loads) and read per element
-    __shared__ __attribute__((aligned(16))) unsigned short sAct[PBR * LDA];      // [row][gate][unit] bf16
-    __shared__ __attribute__((aligned(16))) float sCp[PBR * (PHU + 4)];           // [row][unit]
-    __shared__ __attribute__((aligned(16))) float sDo[PBR * (PHU + 4)];
-    __shared__ int s_len[PBR];
-
-    int group, member;
-    const int ngroups = 2 * (B / PBR);
-    persistent_role(ngroups, NU, group, member);
-    const int dir = group & 1, bs = group >> 1;
-    const int u0 = member * PHU, b0 = bs * PBR;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int c = lane & 15, g = lane >> 4;
-    gu32* gflags = (gu32*)(flags) + group * NU;
-    unsigned base;
-    const bool local = persistent_setup((gu32*)flags, group, NU, member, err, spin_limit, base);
-    if (dbg && threadIdx.x == 0) dbg[(int64_t)blockIdx.x * 8 + 7] = local ? 1 : 0;
-
-    // resident B fragments: bw[nt][k] = W_h[unit w H/4 + 16 nt + c][k H + u0 + 8 g .. + 7]
-    bf16x8 bw[NT][4];
-    {
-        const bf16* wdir = wh + (size_t)dir * H * G4;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                bw[nt][k] = *reinterpret_cast<const bf16x8*>(
-                    wdir + (size_t)(w * (H / 4) + 16 * nt + c) * G4 + k * H + u0 + 8 * g);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) asm volatile("" ::"v"(bw[nt][k]));     // see the gather BPTT
-    }
-    if (tid < PBR) s_len[tid] = seq_len[b0 + tid];
-    __syncthreads();
-
-    const int emt = w >> 1, entl = w & 1;
-    const int ul = 16 * entl + c;                        // the unit (in the slice) of this thread's elements
-    const int rb = 16 * emt + 4 * g;                     // its 4 rows rb .. rb + 3
-    int len[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) len[r] = s_len[rb + r];
-    // row-wise loader item of the epilogue operands: row er, units eu .. eu + 3
-    const int er = tid >> 3, eu = 4 * (tid & 7);
-    const int elen = s_len[er];
-    float dcs[4] = {0.f, 0.f, 0.f, 0.f};
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};               // the bias gradient: dz of (this unit, gate k), own rows
-    // exchange X[parity][group][dst][src][BLK]; a block's element order is the MFMA
-    // output order [mt][n-tile half][lane][r], so producer and consumer lanes move
-    // 4 contiguous elements each
-    const int64_t par_stride = (int64_t)ngroups * NU * NU * BLK;
-    auto x_rsrc = __builtin_amdgcn_make_buffer_rsrc(px, 0, (int)(2 * par_stride * EB), 0x00020000);
-    const int my_off = ((emt * 2 + entl) * 64 + lane) * 4;          // elements, inside a block
-
-    for (int i = 0; i < T; ++i) {
-        const int s = T - 1 - i;
-        pstamp(dbg, i, 0);
-        // 0. epilogue operands (independent of the recurrence): vector loads of row er
-        {
-            const int t = step_time(dir, s, elen);
-            const int64_t tb = ((int64_t)t * B + b0 + er) * 2 + dir;
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-            u32x2 av[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) av[k] = *reinterpret_cast<const u32x2*>(acts_t + tb * G4 + k * H + u0 + eu);
-            const f32x4 cv = *reinterpret_cast<const f32x4*>(cprev_t + tb * H + u0 + eu);
-            const u32x2 dv = *reinterpret_cast<const u32x2*>(dout + ((int64_t)t * B + b0 + er) * 2 * H + dir * H + u0 + eu);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) *reinterpret_cast<u32x2*>(&sAct[er * LDA + k * PHU + eu]) = av[k];
-            *reinterpret_cast<f32x4*>(&sCp[er * (PHU + 4) + eu]) = cv;
-            f32x4 dvf;
-            dvf[0] = __uint_as_float(dv[0] << 16); dvf[1] = __uint_as_float(dv[0] & 0xffff0000u);
-            dvf[2] = __uint_as_float(dv[1] << 16); dvf[3] = __uint_as_float(dv[1] & 0xffff0000u);
-            *reinterpret_cast<f32x4*>(&sDo[er * (PHU + 4) + eu]) = dvf;
-        }
-        float dh[4] = {0.f, 0.f, 0.f, 0.f};
-        if (i > 0) {
-            // 1. every member published its partial products of step i-1 (flag >= i)
-            if (w == 0) {
-                unsigned spins = 0;
-                while (true) {
-                    unsigned f = base + (unsigned)i;
-                    if (lane < NU) f = poll_word(gflags + lane, local);
-                    if (__all(reached(f, base + (unsigned)i))) break;
-                    poll_pause();
-                    if (++spins > spin_limit) {
-                        if (lane == 0) __hip_atomic_fetch_or(err, (unsigned)OCRK_STATUS_LSTM_BWD_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                }
-            }
-            __syncthreads();
-            pstamp(dbg, i, 1);
-            // 2. dh_rec = sum over the NU source members of their block for this member (fixed order)
-            const int64_t boff = ((int64_t)((i - 1) & 1) * par_stride +
-                                  ((int64_t)group * NU + member) * NU * BLK + my_off) * EB;
-            if constexpr (PB16) {
-                typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                u32x2 pv[NU];
-#pragma unroll
-                for (int src = 0; src < NU; ++src)
-                    pv[src] = local ? __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, (int)(boff + (int64_t)src * BLK * EB), 0, 2))
-                                    : __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, (int)(boff + (int64_t)src * BLK * EB), 0, 16));
-#pragma unroll
-                for (int src = 0; src < NU; ++src) {
-                    dh[0] += __uint_as_float(pv[src][0] << 16); dh[1] += __uint_as_float(pv[src][0] & 0xffff0000u);
-                    dh[2] += __uint_as_float(pv[src][1] << 16); dh[3] += __uint_as_float(pv[src][1] & 0xffff0000u);
-                }
-            } else {
-                u32x4 pv[NU];
-#pragma unroll
-                for (int src = 0; src < NU; ++src) pv[src] = get16(x_rsrc, (int)(boff + (int64_t)src * BLK * EB), local);
-#pragma unroll
-                for (int src = 0; src < NU; ++src)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dh[r] += __uint_as_float(pv[src][r]);
-            }
-        } else {
-            __syncthreads();                                 // the staged epilogue operands
-        }
-        // 3. the cell's gradient for (rows rb..rb+3, unit ul); dz to LDS as the MFMA A operand
-        float dz[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = rb + r;
-            const bool valid = s < len[r];
-            const float dhr = dh[r] + sDo[row * (PHU + 4) + ul];
-            const float ai = bits_f(sAct[row * LDA + 0 * PHU + ul]), aj = bits_f(sAct[row * LDA + 1 * PHU + ul]);
-            const float af = bits_f(sAct[row * LDA + 2 * PHU + ul]), ao = bits_f(sAct[row * LDA + 3 * PHU + ul]);
-            const float cp = sCp[row * (PHU + 4) + ul];
-            const float cc = af * cp + ai * aj;
-            const float tc = tanh_fast(cc);
-            const float dc = dcs[r] + dhr * ao * (1.f - tc * tc);
-            dz[3][r] = valid ? dhr * tc * ao * (1.f - ao) : 0.f;
-            dz[0][r] = valid ? dc * aj * ai * (1.f - ai) : 0.f;
-            dz[1][r] = valid ? dc * ai * (1.f - aj * aj) : 0.f;
-            dz[2][r] = valid ? dc * cp * af * (1.f - af) : 0.f;
-            dcs[r] = valid ? dc * af : 0.f;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            bsum[k] += (dz[k][0] + dz[k][1]) + (dz[k][2] + dz[k][3]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sA[(rb + r) * LDA + k * PHU + ul] = bf16_bits(dz[k][r]);
-        __syncthreads();
-        pstamp(dbg, i, 2);
-        if (i + 1 < T) {
-            // 4. P = dz_own . W_h(own gate cols)^T over this wave's H/4 units
-            floatx4 acc[2][NT];
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&sA[c * LDA + k * PHU + 8 * g]);
-                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(&sA[(16 + c) * LDA + k * PHU + 8 * g]);
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, bw[nt][k], acc[0][nt], 0, 0, 0);
-                    acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, bw[nt][k], acc[1][nt], 0, 0, 0);
-                }
-            }
-            // 5. publish the blocks (plain stores stay in the XCD's L2 when the group is
-            //    on one XCD, else write-through), drain, barrier, flag
-            const int64_t pbase = (int64_t)(i & 1) * par_stride + (int64_t)group * NU * NU * BLK;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int dst = (w * (H / 4) + 16 * nt) / PHU;
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt) {
-                    const int64_t off = (pbase + ((int64_t)dst * NU + member) * BLK +
-                                         ((mt * 2 + (nt & 1)) * 64 + lane) * 4) * EB;
-                    if constexpr (PB16) {
-                        const float (&v)[4] = *reinterpret_cast<const float(*)[4]>(&acc[mt][nt]);
-                        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-                        const unsigned long long q = pack4(v);
-                        const u32x2 qq = __builtin_bit_cast(u32x2, q);
-                        if (local) __builtin_amdgcn_raw_buffer_store_b64(qq, x_rsrc, (int)off, 0, 0);
-                        else __builtin_amdgcn_raw_buffer_store_b64(qq, x_rsrc, (int)off, 0, 16);
-                    } else {
-                        const u32x4 v = __builtin_bit_cast(u32x4, acc[mt][nt]);
-                        if (local) __builtin_amdgcn_raw_buffer_store_b128(v, x_rsrc, (int)off, 0, 0);
-                        else __builtin_amdgcn_raw_buffer_store_b128(v, x_rsrc, (int)off, 0, 16);
-                    }
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) raise_flag(gflags + member, base + (unsigned)(i + 1), local);
-        }
-        pstamp(dbg, i, 3);
-        // 6. time-order copy of dz for the weight-gradient GEMMs, 16 B per piece from
-        //    the LDS tile (drains behind the next step; sA is rewritten only after
-        //    the next step's wait barrier)
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int p = tid + 256 * v;
-            const int row = p >> 4, k = (p >> 2) & 3, q = p & 3;
-            const int t = step_time(dir, s, s_len[row]);
-            const u32x4 val = *reinterpret_cast<const u32x4*>(&sA[row * LDA + k * PHU + 8 * q]);
-            *reinterpret_cast<u32x4*>(dG_t + (((int64_t)t * B + b0 + row) * 2 + dir) * G4 + k * H + u0 + 8 * q) = val;
-        }
-        pstamp(dbg, i, 4);
-    }
-    if (bpart) {
-        // the bias partial of (unit ul, gate k) over the member's 32 rows: the
-        // 8 threads holding that unit (4 g x 2 M tiles) meet in LDS, fixed order
-        __syncthreads();
-        float* red = reinterpret_cast<float*>(sAct);                    // [8 row groups][128 gate cols]
-#pragma unroll
-        for (int k = 0; k < 4; ++k) red[(emt * 4 + g) * (4 * PHU) + k * PHU + ul] = bsum[k];
-        __syncthreads();
-        if (tid < 4 * PHU) {
-            float sum = 0.f;
-            for (int q = 0; q < 8; ++q) sum += red[q * (4 * PHU) + tid];
-            bpart[(int64_t)(bs * 2 + dir) * G4 + (tid / PHU) * H + u0 + (tid % PHU)] = sum;
-        }
-    }
-}
-
 // The late-load forms (option PERSIST_LATE=0 disables them); their buffer loads
 // address the largest operand (`bytes`) with 32-bit offsets.
 static bool persist_late(int64_t bytes) { return opt(OPT_PERSIST_LATE) != 0 && bytes < 0x7fffffffll; }
@@ -1473,67 +1111,18 @@ extern "C" int ocrk_lstm_fwd_persistent(const void* gx, const void* whT, const i
     return ocrk::launch_status("ocrk_lstm_fwd_persistent");
 }
 
-#ifdef OCRK_EXPERIMENTS
-// (tools build, include/ocrk_debug.h: measured no gain -- every step 0.7 us longer,
-// profiles/r3_fused_projection.txt)
-// Fused first layer: x [T][B][n_in] (time-major features), wxT [2][4H][n_in] (per
-// direction W_x^T, gate-major rows), bias f32 [2][4H]; everything else as above.
-extern "C" int ocrk_lstm_fwd_persistent_x_supported(int B, int H, int n_in) {
-    if (H != 512 || n_in != 256 || B % PBR) return 0;
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_fwd_persistent_kernel<16, true, 256>, 256, 0) != hipSuccess)
-        return 0;
-    const long grid = 2L * (B / PBR) * (H / PHU);
-    return grid <= (long)cus * per_cu ? 1 : 0;
-}
-
-extern "C" int ocrk_lstm_fwd_persistent_x(const void* x, int n_in, const void* wxT, const float* bias, const void* whT,
-                                          const int* seq_len, int T, int B, int H, void* out, void* hprev_t,
-                                          float* cprev_t, void* acts_t, unsigned* err, unsigned* flags, void* ws,
-                                          size_t ws_bytes, void* stream) {
-    OCRK_REQUIRE(ocrk_lstm_fwd_persistent_x_supported(B, H, n_in),
-                 "ocrk_lstm_fwd_persistent_x: B=%d H=%d n_in=%d unsupported or not co-resident", B, H, n_in);
-    OCRK_REQUIRE(ws_bytes >= ocrk_lstm_fwd_persistent_workspace_size(B, H), "ocrk_lstm_fwd_persistent_x: workspace too small");
-    OCRK_REQUIRE(x && wxT && bias && err, "ocrk_lstm_fwd_persistent_x: null operand");
-    OCRK_REQUIRE((int64_t)T * B * n_in * 2 < 0x7fffffffll, "ocrk_lstm_fwd_persistent_x: x exceeds 2 GB");
-    if (T <= 0) return OCRK_OK;
-    hipStream_t st = ocrk::as_stream(stream);
-    size_t counters = ((size_t)2 * 2 * (B / PBR) * (H / PHU) * sizeof(unsigned) + 127) / 128 * 128;
-    unsigned* cnt = flags ? flags : (unsigned*)ws;
-    bf16* hx = (bf16*)((char*)ws + counters);
-    if (!flags && hipMemsetAsync(cnt, 0, counters, st) != hipSuccess)
-        return ocrk::launch_status("ocrk_lstm_fwd_persistent_x memset");
-    const unsigned grid = 2u * (unsigned)(B / PBR) * (unsigned)(H / PHU);
-    lstm_fwd_persistent_kernel<16, true, 256><<<grid, 256, 0, st>>>(
-        nullptr, (const bf16*)whT, hx, seq_len, T, B, (bf16*)out, (bf16*)hprev_t, cprev_t, (bf16*)acts_t, cnt, err,
-        lstm_spin_limit(), g_lstm_dbg, (const bf16*)x, (const bf16*)wxT, bias);
-    return ocrk::launch_status("ocrk_lstm_fwd_persistent_x");
-}
-#endif  // OCRK_EXPERIMENTS
-
 // ---------------------------------------------------------- backward C ABI
-// OCRK_LSTM_BWD_KSPLIT=1: the K-split form (read per launch). Off by default:
-// measured 5.2 (bf16 partials) / 7.0 (f32) against 4.2 us per step for the
-// gather form at B=256, H=512 -- its exchange buffer (NU x NU blocks per group,
-// 2-4 MB per XCD) does not stay in the XCD's L2 between steps.
-static bool lstm_bwd_ksplit() { return opt(OPT_LSTM_BWD_KSPLIT) == 1; }
-
 extern "C" size_t ocrk_lstm_bwd_persistent_workspace_size(int B, int H) {
-    // flag word + XCC word per workgroup (128-B aligned block), then the exchange buffer:
-    // K-split: [2 parities][groups][NU dst][NU src][32 x 32] f32; gather: [2][2][B][4H] bf16
+    // flag word + XCC word per workgroup (128-B aligned block), then the dz exchange buffer
+    // [2 parities][2 directions][B][4H] bf16
     size_t counters = ((size_t)2 * 2 * (B / PBR) * (H / PHU) * sizeof(unsigned) + 127) / 128 * 128;
-    const size_t nu = (size_t)(H / PHU);
-    const size_t ksplit = (size_t)2 * 2 * (B / PBR) * nu * nu * PBR * PHU * sizeof(float);
-    const size_t gather = (size_t)2 * 2 * B * 4 * H * sizeof(bf16);
-    return counters + (ksplit > gather ? ksplit : gather);
+    return counters + (size_t)2 * 2 * B * 4 * H * sizeof(bf16);
 }
 
 // the 16-row / 64-unit BPTT (H = 512): default where its grid (B workgroups) is co-resident;
 // option LSTM_BWD_R16=0 keeps the 32-row gather kernel (A/B and tests)
 static bool lstm_bwd_r16(int B, int H) {
-    if (opt(OPT_LSTM_BWD_R16) == 0 || H != 512 || B % PBR || lstm_bwd_ksplit()) return false;   // flag words as the gather form
+    if (opt(OPT_LSTM_BWD_R16) == 0 || H != 512 || B % PBR) return false;   // flag words as the gather form
     static ocrk::DeviceOnce once;
     static int per_cu[ocrk::kMaxDevices];
     const int dev = ocrk::current_device();
@@ -1555,16 +1144,8 @@ extern "C" int ocrk_lstm_bwd_persistent_supported(int B, int H) {
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-#ifdef OCRK_EXPERIMENTS
-    hipError_t e = lstm_bwd_ksplit()
-        ? (H == 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_ksplit_kernel<16, false>, 256, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_ksplit_kernel<8, false>, 256, 0))
-        : (H == 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_persistent_kernel<16>, 256, 0)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_persistent_kernel<8>, 256, 0));
-#else
     hipError_t e = H == 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_persistent_kernel<16>, 256, 0)
                             : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lstm_bwd_persistent_kernel<8>, 256, 0);
-#endif
     if (e != hipSuccess) return 0;
     const long grid = 2L * (B / PBR) * (H / PHU);
     return grid <= (long)cus * per_cu ? 1 : 0;
@@ -1589,19 +1170,6 @@ extern "C" int ocrk_lstm_bwd_persistent(const void* wh, const int* seq_len, int 
         return ocrk::launch_status("ocrk_lstm_bwd_persistent");
     }
     const unsigned grid = 2u * (unsigned)(B / PBR) * (unsigned)(H / PHU);
-#ifdef OCRK_EXPERIMENTS
-    if (lstm_bwd_ksplit()) {
-        const bool pb16 = opt(OPT_LSTM_BWD_PB16) == 1;            // partial products exchanged in bf16
-#define KSPLIT_LAUNCH(KSV, PB)                                                                                   \
-        lstm_bwd_ksplit_kernel<KSV, PB><<<grid, 256, 0, st>>>((const bf16*)wh, zx, seq_len, T, B, (const bf16*)dout,  \
-                                                             cprev_t, (const bf16*)acts_t, (bf16*)dG_t, cnt, err,     \
-                                                             lstm_spin_limit(), g_lstm_dbg, dbias_part)
-        if (H == 512) { if (pb16) KSPLIT_LAUNCH(16, true); else KSPLIT_LAUNCH(16, false); }
-        else { if (pb16) KSPLIT_LAUNCH(8, true); else KSPLIT_LAUNCH(8, false); }
-#undef KSPLIT_LAUNCH
-        return ocrk::launch_status("ocrk_lstm_bwd_persistent");
-    }
-#endif
     if (H == 512 && persist_late((int64_t)T * B * 8 * H * 2))
         lstm_bwd_persistent_kernel<16, true><<<grid, 256, 0, st>>>((const bf16*)wh, zx, seq_len, T, B, (const bf16*)dout, cprev_t,
                                                                    (const bf16*)acts_t, (bf16*)dG_t, cnt, err, lstm_spin_limit(), g_lstm_dbg,

@@ -156,6 +156,26 @@ __device__ __forceinline__ void lds_dma16_asm(const i32x4_t& r, void* lds, unsig
                  :: "v"(voff), "s"(r), "{m0}"(a) : "memory");
 }
 
+// ---- shared by the one-wave-per-SIMD engines (gemm_w4.hip, gemm_w4tn.hip)
+
+// a buffer offset past any num_records: the load returns 0, the store is dropped
+constexpr unsigned W4_OOB = 0x80000000u;
+
+// s_barrier that neither the scheduler nor memory operations move across
+__device__ __forceinline__ void w4_barrier() {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// lds_dma16_asm with the LDS byte address as a number and a scalar byte offset (soffset)
+__device__ __forceinline__ void w4_dma16(const i32x4_t& r, unsigned lds, unsigned voff, unsigned soff) {
+    asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
+                 :: "v"(voff), "s"(r), "s"(soff), "{m0}"(lds) : "memory");
+}
+
 // ---- shared by the 256-row tile engines (gemm_pp.hip, gemm_w4.hip, gemm_w4tn.hip)
 
 // work item w -> (output tile, z = batch * splits + slice); tiles in groups

@@ -32,12 +32,11 @@ namespace {
 struct OptDef {
     const char* name;
     int64_t def;
-    bool exp = false;       // measured-slower route: only the tools build (make exp) reads / sets it
 };
 constexpr OptDef kOptDefs[OPT_COUNT] = {
     {"CONV_DIRECT", 1}, {"CONV_ROWS", 1}, {"CONV_ROWS_WIDE", 1}, {"CONV_WGRAD_BLOCKS", 1},
-    {"LSTM_SPIN_LIMIT", 0}, {"PERSIST_LATE", 1}, {"LSTM_BWD_KSPLIT", 0, true}, {"LSTM_BWD_PB16", 0, true},
-    {"LSTM_BWD_R16", 1}, {"CTC_LDS", 1}, {"PP_PERSIST_NK", 8}, {"PP_DEEP", 0, true}, {"NT_F32_EXACT", 1},
+    {"LSTM_SPIN_LIMIT", 0}, {"PERSIST_LATE", 1},
+    {"LSTM_BWD_R16", 1}, {"CTC_LDS", 1}, {"PP_PERSIST_NK", 8}, {"NT_F32_EXACT", 1},
     {"NT_F32_MASK", 1},
     {"NT_F32_X6", 0}, {"BEAM_WAVE", 1}, {"BN_BWD_BLOCKS", 2048}, {"BN_ROUTE", 1}, {"BN_ROUTE_SEG", 8}, {"BN_ROUTE_NCH", 4},
     {"CONV_TN_ITEMS", 192},
@@ -48,18 +47,8 @@ constexpr OptDef kOptDefs[OPT_COUNT] = {
 std::atomic<int64_t> g_opts[OPT_COUNT];
 std::once_flag g_opts_once;
 
-#ifdef OCRK_EXPERIMENTS
-constexpr bool kExperiments = true;
-#else
-constexpr bool kExperiments = false;
-#endif
-
 void init_opts() {
     for (int i = 0; i < OPT_COUNT; ++i) {
-        if (kOptDefs[i].exp && !kExperiments) {          // the product library: the default, always
-            g_opts[i].store(kOptDefs[i].def, std::memory_order_relaxed);
-            continue;
-        }
         char env[64];
         snprintf(env, sizeof(env), "OCRK_%s", kOptDefs[i].name);
         const char* e = getenv(env);
@@ -71,7 +60,7 @@ int find_opt(const char* name) {
     if (!name) return -1;
     if (!strncmp(name, "OCRK_", 5)) name += 5;
     for (int i = 0; i < OPT_COUNT; ++i)
-        if (!strcmp(name, kOptDefs[i].name)) return kOptDefs[i].exp && !kExperiments ? -1 : i;
+        if (!strcmp(name, kOptDefs[i].name)) return i;
     return -1;
 }
 }  // namespace
@@ -147,78 +136,6 @@ int ocrk_timer_record(void* ev, void* stream) {
     }
     return OCRK_OK;
 }
-
-#ifdef OCRK_EXPERIMENTS
-// include/ocrk_debug.h (tools build): fence-less stream forks and CU-masked streams.
-// Both measured no gain in the train step; a CU-masked stream is a
-// BLOCKING stream (hipExtStreamCreateWithCUMask takes no flags), so beside work on the
-// legacy NULL stream it serialises with it.
-int ocrk_stream_wait(void* waiter, void* signaller, int mode) {
-    OCRK_REQUIRE(mode >= 0 && mode <= 2, "ocrk_stream_wait: mode %d", mode);
-    constexpr int RING = 64, MAXDEV = 64;
-    static std::mutex mu;
-    static hipEvent_t ring[MAXDEV][3][RING] = {};
-    static int next[MAXDEV][3] = {};
-    int dev = 0;
-    // the events live on the signaller's device (a ring per device and mode)
-    if (hipStreamGetDevice(ocrk::as_stream(signaller), &dev) != hipSuccess || dev < 0 || dev >= MAXDEV)
-        return ocrk::launch_status("ocrk_stream_wait");
-    std::lock_guard<std::mutex> lk(mu);
-    const int i = next[dev][mode];
-    hipEvent_t& ev = ring[dev][mode][i];
-    if (!ev) {
-        const unsigned fl = hipEventDisableTiming |
-                            (mode == 1 ? hipEventDisableSystemFence : mode == 2 ? hipEventReleaseToDevice : 0u);
-        int cur = 0;
-        hipError_t ce = hipGetDevice(&cur);
-        if (ce == hipSuccess && cur != dev) ce = hipSetDevice(dev);   // created on the signaller's device
-        if (ce == hipSuccess) ce = hipEventCreateWithFlags(&ev, fl);
-        if (cur != dev) {
-            const hipError_t re = hipSetDevice(cur);
-            if (ce == hipSuccess) ce = re;
-        }
-        if (ce != hipSuccess) {
-            ocrk::set_error("ocrk_stream_wait create: %s", hipGetErrorString(ce));
-            return OCRK_ERR_HIP;
-        }
-    }
-    next[dev][mode] = (i + 1) % RING;
-    hipError_t e = hipEventRecord(ev, ocrk::as_stream(signaller));
-    if (e == hipSuccess) e = hipStreamWaitEvent(ocrk::as_stream(waiter), ev, 0);
-    if (e != hipSuccess) {
-        ocrk::set_error("ocrk_stream_wait: %s", hipGetErrorString(e));
-        return OCRK_ERR_HIP;
-    }
-    return OCRK_OK;
-}
-
-int ocrk_stream_create_cu_limited(int n_cus, void** stream) {
-    OCRK_REQUIRE(stream != nullptr && n_cus > 0, "ocrk_stream_create_cu_limited: n_cus %d / null slot", n_cus);
-    const int total = ocrk::cu_count();
-    uint32_t mask[ocrk::kMaxCuWords] = {};
-    OCRK_REQUIRE(total <= 32 * ocrk::kMaxCuWords, "ocrk_stream_create_cu_limited: %d CUs", total);
-    // keep n of every `total` CUs, the left-out ones evenly spaced over the CU
-    // order (so every XCD / shader engine keeps some for other streams)
-    const int keep = n_cus < total ? n_cus : total;
-    for (int i = 0; i < total; ++i) {
-        const bool on = (int64_t)(i + 1) * keep / total != (int64_t)i * keep / total;
-        if (on) mask[i / 32] |= 1u << (i % 32);
-    }
-    hipStream_t s = nullptr;
-    const hipError_t e = hipExtStreamCreateWithCUMask(&s, (uint32_t)((total + 31) / 32), mask);
-    if (e != hipSuccess) {
-        ocrk::set_error("ocrk_stream_create_cu_limited: %s", hipGetErrorString(e));
-        return OCRK_ERR_HIP;
-    }
-    *stream = s;
-    return OCRK_OK;
-}
-
-int ocrk_stream_destroy(void* stream) {
-    if (stream) (void)hipStreamDestroy(ocrk::as_stream(stream));
-    return OCRK_OK;
-}
-#endif  // OCRK_EXPERIMENTS
 
 int ocrk_timer_elapsed(void* ev0, void* ev1, float* ms) {
     OCRK_REQUIRE(ev0 && ev1 && ms, "ocrk_timer_elapsed: null argument");

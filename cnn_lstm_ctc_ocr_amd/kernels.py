@@ -105,18 +105,6 @@ def conv12_fwd(x, w1, b1, w_nk2, b2, want_y1=True):
     return y1, bits, z, stats
 
 
-def conv2_bwd_weight_c1x(x, w1, b1, dz, dw, accumulate=True):
-    """conv2's weight gradient with y1 = relu(conv1(x)) recomputed from the image x [B,IH,IW]
-    (u8 or bf16) instead of read (ocrk_conv2_bwd_weight_c1x); dz [B,IH-2,IW-2,32] bf16.
-    Tools build only (include/ocrk_debug.h): +55 us in the step, not the model's route."""
-    _chk(x, w1, b1, dz, dw)
-    B, IH, IW = x.shape[:3]
-    nb = _lib.lib().ocrk_conv3x3_wgrad_workspace_size(B, IH - 2, IW - 2, 32, 32)
-    ws = _ws(nb, x.device)
-    call("ocrk_conv2_bwd_weight_c1x", ptr(x), int(x.dtype == torch.uint8), B, IH, IW, ptr(w1), ptr(b1), ptr(dz),
-         ptr(dw), int(accumulate), ptr(ws), nb, BF16, _stream(x))
-
-
 def conv1_bwd_weight(x, dz, dw, db, accumulate=True):
     _chk(x, dz, dw, db)
     B, H, W = x.shape[0], x.shape[1], x.shape[2]
@@ -646,37 +634,6 @@ def lstm_fwd(gx, whT, seq_len, T, B, H, dtype, save=True):
     return out, hprev, cprev, acts
 
 
-def lstm_fused_x_ok(B, H, n_in, dtype):
-    """Can the tools build (include/ocrk_debug.h) run the first layer's input
-    projection fused into the persistent forward (ocrk_lstm_fwd_persistent_x)?
-    Never the model's route: measured at B=256 it removes the 109 us projection
-    GEMM but makes every step 0.7 us longer (3.40 vs 2.68 us: the x.W_x MFMAs and
-    the x-row DMA land on the step's critical path), 480 vs 490 us for GEMM +
-    loop alone and 5.865 vs 5.847 ms for the train step
-    (profiles/r3_fused_projection.txt)."""
-    if not lstm_persistent_ok(B, H, dtype) or not hasattr(_lib.lib(), "ocrk_lstm_fwd_persistent_x_supported"):
-        return False
-    return bool(_lib.lib().ocrk_lstm_fwd_persistent_x_supported(B, H, n_in))
-
-
-def lstm_fwd_fused_x(x, wxT, bias, whT, seq_len, T, B, H):
-    """The persistent forward with x . W_x + b fused (no gx): x [T,B,In] bf16,
-    wxT [8H, In] (fw | bw W_x^T), bias f32 [8H]. Same outputs as lstm_fwd."""
-    _chk(x, wxT, bias, whT, seq_len)
-    dev = x.device
-    n_in = x.shape[-1]
-    out = torch.empty(T, B, 2 * H, dtype=x.dtype, device=dev)
-    hprev = torch.empty(T, B, 2, H, dtype=x.dtype, device=dev)
-    cprev = torch.empty(T, B, 2, H, dtype=torch.float32, device=dev)
-    acts = torch.empty(T, B, 2, 4 * H, dtype=x.dtype, device=dev)
-    nb = _lib.lib().ocrk_lstm_fwd_persistent_workspace_size(B, H)
-    ws = _ws(nb, dev)
-    call("ocrk_lstm_fwd_persistent_x", ptr(x), n_in, ptr(wxT), ptr(bias), ptr(whT), ptr(seq_len), T, B, H, ptr(out),
-         ptr(hprev), ptr(cprev), ptr(acts), ptr(lstm_error_word(dev)), ptr(persistent_flags("lstm_fwd_x", B, H, dev)),
-         ptr(ws), nb, _stream(x))
-    return out, hprev, cprev, acts
-
-
 def lstm_bwd(wh, seq_len, dout, cprev, acts, T, B, H, dbias=None, defer=None):
     """dG [T,B,2,4H]. dbias (f32 [2*4H], accumulated): the layer's bias gradient
     (both directions); the persistent loop forms it in-kernel (per-slice
@@ -824,30 +781,6 @@ def permute3(x, d0, d1, d2, dtype, out=None):
     out = out if out is not None else torch.empty(d1, d0, d2, dtype=dtype, device=x.device)
     call("ocrk_permute3", ptr(x), dtype_code(x.dtype), d0, d1, d2, ptr(out), dtype_code(out.dtype), _stream(x))
     return out
-
-
-def stream_wait(waiter, signaller, mode=1):
-    """`waiter` (a torch.cuda.Stream) waits for the work issued so far on
-    `signaller` (ocrk_stream_wait: an event without the system-scope release).
-    Tools build only (include/ocrk_debug.h, OCRK_LIB=tools/libocrk_exp.so): the
-    fence-less forks measured box-dependent (-35 to +25 us per step)."""
-    call("ocrk_stream_wait", ctypes.c_void_p(waiter.cuda_stream), ctypes.c_void_p(signaller.cuda_stream), int(mode))
-
-
-_CU_STREAMS = []        # (handle, ExternalStream): kept for the process
-
-
-def cu_limited_stream(device, n_cus):
-    """torch.cuda.ExternalStream over ocrk_stream_create_cu_limited(n_cus) on `device`
-    (tools build only). A BLOCKING stream: beside a step on the legacy NULL stream it
-    serialises with it; beside a non-blocking step stream masks of 96-192 CUs measured
-    no change (profiles/r6_stream_ab.txt)."""
-    with torch.cuda.device(device):
-        h = ctypes.c_void_p()
-        call("ocrk_stream_create_cu_limited", int(n_cus), ctypes.byref(h))
-        st = torch.cuda.ExternalStream(h.value, device=device)
-    _CU_STREAMS.append((h, st))
-    return st
 
 
 def fork(waiter, signaller):

@@ -35,7 +35,6 @@ _HOST_DEFAULTS = {
     "TN_ITEMS_L1": 160,       # layer 1 (beside the conv backward)
 }
 # kernel-side options (libocrk's registry, csrc/common.h)
-# (LSTM_BWD_KSPLIT, LSTM_BWD_PB16 and PP_DEEP exist in the tools build only)
 KERNEL_OPTIONS = ("CONV_DIRECT", "CONV_ROWS", "CONV_ROWS_WIDE", "CONV_WGRAD_BLOCKS", "LSTM_SPIN_LIMIT",
                   "PERSIST_LATE", "LSTM_BWD_R16", "CTC_LDS",
                   "PP_PERSIST_NK", "NT_F32_EXACT", "NT_F32_MASK",

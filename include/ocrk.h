@@ -94,8 +94,7 @@ const char* ocrk_last_error(void);
  * BN_ROUTE_NCH, CONV_TN_ITEMS, CONV_TN4_ITEMS,
  * CONV_WGRAD_CUS, F32_MFMA, GEMM_NT, GEMM_NT_STAGED, GEMM_PP, GEMM_PPTN, PP_MIN_N, GEMM_TN, LSTM_DMA,
  * LSTM_BWD_DMA, LSTM_FWD_R16, NT_TAP_UNIFORM, GEMM_W4, GEMM_W4_LAUNCHES (meanings in csrc/common.h). Unknown name: OCRK_ERR_INVALID_ARG.
- * `prev` may be NULL. (LSTM_BWD_KSPLIT, LSTM_BWD_PB16 and PP_DEEP: the tools build
- * only -- routes measured slower, not compiled into this library.) */
+ * `prev` may be NULL. */
 int ocrk_set_option(const char* name, int64_t value, int64_t* prev);
 
 /* x = hi + lo, hi = bf16(x), lo = bf16(x - hi) (round to nearest even; |x - hi - lo| <=

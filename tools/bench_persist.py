@@ -1,5 +1,5 @@
 """Persistent recurrent loops alone (diagnostics): per-step time of the
-persistent LSTM forward / BPTT at the bench shape, both BPTT forms, and the
+persistent LSTM forward / BPTT at the bench shape, and the
 in-kernel s_memrealtime stamps of one mid-sequence step.
     python tools/bench_persist.py [B] [H]"""
 import os
@@ -40,7 +40,6 @@ def timed(fn, reps=5):
 
 os.environ["OCRK_PERSIST_LATE"] = "0"
 f0 = timed(lambda: K.lstm_fwd(gx, whT, seq, T, B, H, torch.bfloat16))
-os.environ["OCRK_LSTM_BWD_KSPLIT"] = "0"
 b0 = timed(lambda: K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H))
 ref_fwd = K.lstm_fwd(gx, whT, seq, T, B, H, torch.bfloat16)[0].float()
 ref_bwd = K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H).float()
@@ -50,26 +49,14 @@ late_fwd = K.lstm_fwd(gx, whT, seq, T, B, H, torch.bfloat16)[0].float()
 late_bwd = K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H).float()
 torch.cuda.synchronize()
 print(f"late loads: fwd {f0:.2f} -> {f:.2f} us/step (max diff {(late_fwd - ref_fwd).abs().max().item():.1e}); "
-      f"gather bwd {b0:.2f} -> (below) (max diff {(late_bwd - ref_bwd).abs().max().item():.1e})", flush=True)
-res, outs = {}, {}
-for form, pb in (("1", "0"), ("1", "1"), ("0", "0")):
-    os.environ["OCRK_LSTM_BWD_KSPLIT"], os.environ["OCRK_LSTM_BWD_PB16"] = form, pb
-    res[form + pb] = timed(lambda: K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H))
-    outs[form + pb] = K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H).float()
-torch.cuda.synchronize()
-os.environ["OCRK_LSTM_BWD_PB16"] = "0"
-dg = outs["00"]
-d = {k: ((v - dg).norm() / dg.norm()).item() for k, v in outs.items()}
-print(f"B={B} H={H} T={T}: fwd {f:.2f} us/step; bwd K-split f32 {res['10']:.2f}, K-split bf16 {res['11']:.2f}, "
-      f"gather {res['00']:.2f} us/step; rel diff vs gather: f32 {d['10']:.2e} bf16 {d['11']:.2e}; "
-      f"status {K.read_status(dev)}", flush=True)
+      f"bwd {b0:.2f} -> (below) (max diff {(late_bwd - ref_bwd).abs().max().item():.1e})", flush=True)
+b = timed(lambda: K.lstm_bwd(wh, seq, dout, cprev, acts, T, B, H))
+print(f"B={B} H={H} T={T}: fwd {f:.2f} us/step; bwd {b:.2f} us/step; status {K.read_status(dev)}", flush=True)
 
 names = {"fwd": ["start", "flags seen", "h staged", "gates spilled", "h published", "saved stored"],
-         "ksplit": ["start", "flags seen", "dz in LDS", "P published", "dG stored"],
-         "gather": ["start", "flags seen", "partials met", "dz published", "dG stored"]}
-for kind in ("fwd", "ksplit", "gather"):
+         "bwd": ["start", "flags seen", "partials met", "dz published", "dG stored"]}
+for kind in ("fwd", "bwd"):
     dbg = torch.zeros(4096 * 8, dtype=torch.int64, device=dev)
-    os.environ["OCRK_LSTM_BWD_KSPLIT"] = "0" if kind == "gather" else "1"
     _lib.call("ocrk_lstm_debug_stamps", _lib.ptr(dbg))
     if kind == "fwd":
         K.lstm_fwd(gx, whT, seq, T, B, H, torch.bfloat16)

@@ -1,10 +1,11 @@
 """Ping-pong GEMM engine (csrc/gemm_pp.hip) on the train step's shapes:
 time per launch, TFLOP/s and the error against a float32 torch reference
 computed from the same bf16 operands (diagnostic; the parity tests are in
-tests/).
+tests/). The convolution rows time the routed conv engines beside them: the
+ping-pong engine has no convolution form.
 
     python tools/bench_pp.py                 # default routing (engine on)
-    OCRK_GEMM_PP=0 python tools/bench_pp.py  # previous engines (hipBLASLt / NT)
+    OCRK_GEMM_PP=0 python tools/bench_pp.py  # the plain GEMMs on the NT engine
     python tools/bench_pp.py --ab [reps]     # the plain GEMMs, GEMM_W4=0 against GEMM_W4=2 (the
                                              # one-wave-per-SIMD engine, csrc/gemm_w4.hip): interleaved in
                                              # this process, `reps` (5) repetitions of 20 launches each
