@@ -52,6 +52,9 @@ SIGNATURES = {
     "ocrk_ctc_spot": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p],
     "ocrk_ctc_field_workspace_size": [_i32, _i32, _i32, _i32, _i32],
     "ocrk_ctc_field": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p],
+    "ocrk_ctc_keyed_field_workspace_size": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "ocrk_ctc_keyed_field": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _f32,
+                             _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p],
     "ocrk_ctc_greedy_decode": [_p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p],
     "ocrk_ctc_beam_workspace_size": [_i32, _i32, _i32],
     "ocrk_gru_fwd_step": [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _p],

@@ -42,16 +42,7 @@
 // of 3..16 symbols, the C entry, case-sensitive): 16 / 512, a pair per wave, 28.3 us; 8 / 256 29.9; 32 / 1024
 // 34.3; 64 / 1024 57.8, 64 / 512 75.9, 64 / 256 151.6 (64 workgroups leave three quarters of the CUs idle: a
 // list of keywords is short, so the rows alone do not fill the device). Without pairing 64 / 1024 takes 94.8.
-#define SPOT_THREADS 512
-#define SPOT_WAVES (SPOT_THREADS / 64)
-#define SPOT_KW 16                       // keywords per workgroup: one pair per wave behind one table copy
-#define SPOT_MAX_LEN 32                  // S = 2 n - 1 <= 63: one state per lane
-#define SPOT_PAIR_LEN 16                 // S <= 31: two such keywords share a wave
-#define SPOT_MAX_WIDTH 255               // the label tensor's width (the other CTC entries' limit)
-#define SPOT_LDS_MAX (112 * 1024)        // the table's LDS budget (the lexicon scorer's)
-#define SPOT_MAX_KW (1 << 20)
-#define SPOT_MAX_B 65535                 // rows ride the grid's y dimension
-#define SPOT_PREP_THREADS 256
+// SPOT_KW, SPOT_THREADS and the kernel itself are in ctc_lattice.h: the keyed field reader runs it too.
 
 __global__ void __launch_bounds__(SPOT_PREP_THREADS)
 spot_prep_kernel(const float* __restrict__ logits, const int* __restrict__ seq_len, int T, int B, int C,
@@ -62,207 +53,14 @@ spot_prep_kernel(const float* __restrict__ logits, const int* __restrict__ seq_l
         ctc_rel_frame<SPOT_PREP_THREADS>(logits, seq_len, T, B, C, tab);
         return;
     }
-    // one thread per keyword, with no row in sight. A bad length never indexes the label rows; a bad label
-    // or alternative is only ever compared.
+    // one thread per keyword, with no row in sight (spot_check_keyword, ctc_lattice.h)
     const int k = ((int)blockIdx.x - frame_blocks) * SPOT_PREP_THREADS + threadIdx.x;
     if (k >= n_kw) return;
-    const int len = kw_len[k];
-    int code = 0, req = -1;
-    if (len < 1 || len > SPOT_MAX_LEN || len > max_kw_len) {
-        code = 2;
-    } else {
-        const int* lab = kw + (size_t)k * max_kw_len;
-        const int* alt = kw_alt ? kw_alt + (size_t)k * max_kw_len : nullptr;
-        bool bad = false;
-        int reps = 0, pl = -1, pa = -1;
-        for (int i = 0; i < len; ++i) {
-            const int l = lab[i], a = alt ? alt[i] : -1;
-            bad |= l < 0 || l >= C - 1 || a < -1 || a >= C - 1;
-            // positions whose sets {l, a} overlap need the blank between them (pl < 0 at i = 0 matches nothing)
-            reps += l == pl || l == pa || (a >= 0 && (a == pl || a == pa));
-            pl = l;
-            pa = a;
-        }
-        if (bad) code = 3;
-        else req = len + reps;
-    }
+    int req;
+    const int code = spot_check_keyword(kw, kw_alt, kw_len, k, max_kw_len, C, req);
     kinfo[k] = req;
     if (kw_status) kw_status[k] = code;
     if (code && status_word) __hip_atomic_fetch_or(status_word, 1u << code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// wave_shr1 for an int: lane i takes lane i - 1, lane 0 takes -1
-__device__ __forceinline__ int spot_shr1(int v) { return __builtin_amdgcn_update_dpp(-1, v, 0x138, 0xf, 0xf, false); }
-
-// The best placement of one keyword on one wave (PAIR: of two, one per 32-lane
-// half; lab, alt and len then differ between the halves, a lane's state is
-// lane & 31 and state 0 of the upper half must not take lane 31's value from the
-// whole-wave shift; two back is masked by skip already, state 1 never skips).
-// tab is the row's [L][C] table of rel (LDS, or the workspace when !LDS); the
-// emissions of step t + D are read while step t computes. len is 0 for a
-// keyword that is not to be scored here (invalid, needs more than L frames, or
-// past the list's end): no lane is active and the result is -inf, (-1, -1).
-// The result is returned on every lane of the keyword's half.
-template <bool LDS, bool ALT, bool PAIR>
-__device__ __forceinline__ void spot_best(const float* __restrict__ tab, const int* __restrict__ lab,
-                                          const int* __restrict__ alt, int len, int L, int C, float& score,
-                                          int& first, int& end) {
-    constexpr int D = LDS ? 1 : 4;                         // one step ahead covers the LDS latency
-    const int wlane = threadIdx.x & 63, s = PAIR ? wlane & 31 : wlane, S = 2 * len - 1;
-    const bool active = s < S, sym = active && !(s & 1);   // then label index s >> 1 < len
-    const int i = s >> 1;
-    const int c0 = sym ? lab[i] : C - 1;
-    int c1 = c0;                                           // no alternative: the same class twice, max(x, x) = x
-    bool skip = false;
-    if (sym && i >= 1) {
-        const int pl = lab[i - 1];
-        skip = c0 != pl;
-        if constexpr (ALT) {
-            const int a = alt[i], pa = alt[i - 1];
-            skip = skip && c0 != pa && (a < 0 || (a != pl && a != pa));
-        }
-    }
-    if constexpr (ALT) {
-        if (sym && alt[i] >= 0) c1 = alt[i];
-    }
-    auto emit = [&](int t) {
-        const float e = tab[t * C + c0];
-        if constexpr (ALT) return fmaxf(e, tab[t * C + c1]);
-        return e;
-    };
-    float V = -INFINITY, best_v = -INFINITY, en[D];
-    int st = -1, best_f = -1, best_e = -1;
-#pragma unroll
-    for (int d = 0; d < D; ++d) en[d] = emit(min(d, L - 1));
-    auto step = [&](float e, int t) {
-        float v1 = wave_shr1(V);
-        int s1 = spot_shr1(st);
-        const float v2 = wave_shr1(v1);
-        const int s2 = spot_shr1(s1);
-        if constexpr (PAIR) v1 = s == 0 ? -INFINITY : v1;
-        float b = V;                                       // stay
-        int bs = st;
-        if (v1 > b) {                                      // one back, only if strictly greater
-            b = v1;
-            bs = s1;
-        }
-        if (skip && v2 > b) {                              // two back, where the two symbol sets are disjoint
-            b = v2;
-            bs = s2;
-        }
-        if (s == 0 && 0.f > b) {                           // entry: the filler before the hit scores 0
-            b = 0.f;
-            bs = t;
-        }
-        V = active ? b + e : -INFINITY;
-        st = bs;
-        if (V > best_v) {                                  // read on the lane of state S - 1 only
-            best_v = V;
-            best_f = st;
-            best_e = t + 1;
-        }
-    };
-    // D whole steps per trip, the read ahead clamped to the last frame instead of predicated
-    int t0 = 0;
-    for (; t0 + D <= L; t0 += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            const float e = en[d];
-            en[d] = emit(min(t0 + d + D, L - 1));
-            step(e, t0 + d);
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-        if (t0 + d < L) step(en[d], t0 + d);
-    const int src = (PAIR ? wlane & 32 : 0) + max(S - 1, 0);
-    score = __shfl(best_v, src, 64);
-    first = __shfl(best_f, src, 64);
-    end = __shfl(best_e, src, 64);
-}
-
-template <bool LDS, bool ALT>
-__global__ void __launch_bounds__(SPOT_THREADS)
-spot_score_kernel(const float* __restrict__ tab_g, const int* __restrict__ seq_len, int T, int C,
-                  const int* __restrict__ kw, const int* __restrict__ kw_alt, const int* __restrict__ kw_len,
-                  const int* __restrict__ kinfo, int n_kw, int max_kw_len, float* __restrict__ score,
-                  int* __restrict__ span) {
-    extern __shared__ float4 s_dyn4[];                     // LDS: the row's table, [L][C]
-    const int b = blockIdx.y;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int L = min(max(seq_len[b], 0), T);
-    const int k0 = blockIdx.x * SPOT_KW;
-    float* out_v = score + (size_t)b * n_kw;
-    int2* out_s = reinterpret_cast<int2*>(span) + (size_t)b * n_kw;
-    const float* tab_b = tab_g + (size_t)b * T * C;
-
-    // a chunk with nothing to score (every keyword too long for this row, or not valid; L == 0)
-    bool feasible = false;
-    if (threadIdx.x < SPOT_KW && k0 + (int)threadIdx.x < n_kw) {
-        const int req = kinfo[k0 + threadIdx.x];
-        feasible = req >= 0 && req <= L;                   // req >= 1: never with L == 0
-    }
-    if (!__syncthreads_or(feasible)) {
-        if (threadIdx.x < SPOT_KW && k0 + (int)threadIdx.x < n_kw) {
-            out_v[k0 + threadIdx.x] = -INFINITY;
-            out_s[k0 + threadIdx.x] = make_int2(-1, -1);
-        }
-        return;
-    }
-    const float* tab = tab_b;
-    if constexpr (LDS) {
-        const int n = L * C;                               // <= T C floats = the launch's dynamic LDS
-        if ((C & 3) == 0) {                                // rows of whole float4s: tab_b is 16-B aligned
-            const float4* src = reinterpret_cast<const float4*>(tab_b);
-            for (int i = threadIdx.x; i < (n >> 2); i += SPOT_THREADS) s_dyn4[i] = src[i];
-        } else {
-            float* dst = reinterpret_cast<float*>(s_dyn4);
-            for (int i = threadIdx.x; i < n; i += SPOT_THREADS) dst[i] = tab_b[i];
-        }
-        __syncthreads();
-        tab = reinterpret_cast<const float*>(s_dyn4);
-    }
-    // a wave takes the adjacent keywords 2 p and 2 p + 1 together: both on one pass of the recursion when
-    // neither needs more than half a wave, else one after the other
-    for (int p = wave; 2 * p < SPOT_KW; p += SPOT_WAVES) {
-        int k[2], len[2];                                  // wave-uniform
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            k[h] = k0 + 2 * p + h;
-            const int req = k[h] < n_kw ? __builtin_amdgcn_readfirstlane(kinfo[k[h]]) : -1;
-            // scored: then the length is in [1, min(32, max_kw_len)]
-            len[h] = req >= 0 && req <= L ? __builtin_amdgcn_readfirstlane(kw_len[k[h]]) : 0;
-        }
-        if (k[0] >= n_kw) break;
-        if (len[0] <= SPOT_PAIR_LEN && len[1] <= SPOT_PAIR_LEN) {
-            const int h = lane >> 5, kh = h ? k[1] : k[0];
-            float v = -INFINITY;
-            int f = -1, e = -1;
-            if (len[0] | len[1])
-                spot_best<LDS, ALT, true>(tab, kw + (size_t)min(kh, n_kw - 1) * max_kw_len,
-                                          ALT ? kw_alt + (size_t)min(kh, n_kw - 1) * max_kw_len : nullptr,
-                                          h ? len[1] : len[0], L, C, v, f, e);
-            if ((lane & 31) == 0 && kh < n_kw) {
-                out_v[kh] = v;
-                out_s[kh] = make_int2(f, e);
-            }
-            continue;
-        }
-#pragma unroll 1
-        for (int h = 0; h < 2; ++h) {
-            const int kh = h ? k[1] : k[0], n = h ? len[1] : len[0];
-            if (kh >= n_kw) break;
-            float v = -INFINITY;
-            int f = -1, e = -1;
-            if (n)
-                spot_best<LDS, ALT, false>(tab, kw + (size_t)kh * max_kw_len,
-                                           ALT ? kw_alt + (size_t)kh * max_kw_len : nullptr, n, L, C, v, f, e);
-            if (lane == 0) {
-                out_v[kh] = v;
-                out_s[kh] = make_int2(f, e);
-            }
-        }
-    }
 }
 
 // ------------------------------------------------------------------- C ABI
@@ -284,10 +82,10 @@ static void spot_launch(dim3 grid, size_t dyn, hipStream_t s, const float* tab, 
                         int max_kw_len, float* score, int* span) {
     if constexpr (LDS) {
         static ocrk::DeviceOnce attr;
-        ocrk::set_dyn_lds(attr, reinterpret_cast<const void*>(&spot_score_kernel<true, ALT>), SPOT_LDS_MAX);
+        ocrk::set_dyn_lds(attr, reinterpret_cast<const void*>(&spot_score_kernel<true, ALT, false>), SPOT_LDS_MAX);
     }
-    spot_score_kernel<LDS, ALT><<<grid, SPOT_THREADS, dyn, s>>>(tab, seq_len, T, C, kw, kw_alt, kw_len, kinfo, n_kw,
-                                                               max_kw_len, score, span);
+    spot_score_kernel<LDS, ALT, false><<<grid, SPOT_THREADS, dyn, s>>>(tab, seq_len, T, C, kw, kw_alt, kw_len, kinfo,
+                                                                      n_kw, max_kw_len, score, span, nullptr);
 }
 
 extern "C" int ocrk_ctc_spot(const float* logits, const int* seq_len, int T, int B, int C, const int* kw,

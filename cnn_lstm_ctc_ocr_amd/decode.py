@@ -15,6 +15,9 @@ KeywordSet / ctc_keyword_spotter find keywords inside a line on the same logits
 FieldSet / ctc_field_reader read the best string matching a small character-class
 pattern out of a line on the same logits (extractor.py's amount, GST and receipt
 number regexes over the 1-best string), for server.FieldRecognition.
+KeyedFieldSet / ctc_keyed_field_reader pair the two on the lattice: the string
+matching a pattern that follows one of a field's keywords (extractor.py's
+KWDetector / KWExtractor pairing), for server.KeyedRecognition.
 Sparse outputs are returned dense, -1 padded (what sparse_tensor_to_dense(-1)
 gives the reference, validate.py:91-92), plus per-row lengths.
 """
@@ -425,6 +428,111 @@ def ctc_field_reader(inputs, sequence_length, fields):
     cls, opt, ln = fields.tensors(inputs.device)
     score, span, text, _status = K.ctc_field(_f32(inputs), sequence_length.to(torch.int32).contiguous(), cls, opt, ln)
     return score, span, text
+
+
+class KeyedFieldSet:
+    """Named keyed fields to read out of recognised lines: a mapping name ->
+    (keywords, pattern), "the string matching `pattern` that follows one of
+    `keywords` on the line" (what src/extract_fields/extractor.py's KWDetector /
+    KWExtractor pair produces: {'total': [...], 'gst': [...]}), e.g.
+    {"total": (["total", "amount", "ttl"], r"[1-9]\\d{0,3}\\.\\d{1,2}")}.
+    Each field's keywords are validated and encoded as a KeywordSet does (its
+    ValueErrors, its 32-character limit, case_insensitive's alternatives;
+    duplicates are judged within a field, so two fields may share a keyword) and
+    its pattern goes through compile_field. Kept as one flat keyword list with
+    each keyword's field index, and dense int32 tensors per device. ValueError
+    for an empty mapping, a value that is not a (keywords, pattern) pair, or
+    anything KeywordSet or compile_field refuses. Pickles as its arguments."""
+
+    def __init__(self, mapping, case_insensitive=False):
+        if not hasattr(mapping, "items"):
+            raise TypeError("KeyedFieldSet: mapping is a mapping name -> (keywords, pattern), "
+                            f"not {type(mapping).__name__}")
+        mapping = dict(mapping)
+        if not mapping:
+            raise ValueError("KeyedFieldSet: the mapping is empty")
+        self.case_insensitive = bool(case_insensitive)
+        sets, compiled, clean = [], [], {}
+        for name, value in mapping.items():
+            if not isinstance(name, str):
+                raise ValueError(f"KeyedFieldSet: the name {name!r} is {type(name).__name__}, not a string")
+            if isinstance(value, str) or not hasattr(value, "__len__") or len(value) != 2:
+                raise ValueError(f"KeyedFieldSet: {name!r} maps to a pair (keywords, pattern)")
+            keywords, pattern = value
+            if isinstance(keywords, str) or not hasattr(keywords, "__iter__"):
+                raise ValueError(f"KeyedFieldSet: {name!r}: keywords is a sequence of strings, "
+                                 f"not {type(keywords).__name__}")
+            try:
+                sets.append(KeywordSet(keywords, self.case_insensitive))
+            except ValueError as e:
+                raise ValueError(f"KeyedFieldSet: {name!r}: {e}") from None
+            compiled.append(compile_field(name, pattern))
+            clean[name] = (list(sets[-1].keywords), pattern)
+        self.mapping = clean
+        self.names = tuple(clean)
+        self.compiled = tuple(compiled)
+        self.keywords = tuple(w for s in sets for w in s.keywords)             # the flat list kw_index points into
+        self.groups = np.concatenate([np.full(len(s), a, np.int32) for a, s in enumerate(sets)])
+        self.kw_lengths = np.concatenate([s.lengths for s in sets])
+        self.labels = np.zeros((len(self.keywords), int(self.kw_lengths.max())), np.int32)
+        self.alternatives = np.full(self.labels.shape, -1, np.int32)
+        k = 0
+        for s in sets:
+            self.labels[k:k + len(s), :s.labels.shape[1]] = s.labels
+            self.alternatives[k:k + len(s), :s.labels.shape[1]] = s.alternatives
+            k += len(s)
+        self.lengths = np.array([len(c) for c, _ in self.compiled], np.int32)
+        width = int(self.lengths.max())
+        self.classes = np.full((len(self.compiled), width, MAX_FIELD_CLASS), -1, np.int32)
+        self.optional = np.zeros((len(self.compiled), width), np.int32)
+        for p, (cls, opt) in enumerate(self.compiled):
+            for i, labels in enumerate(cls):
+                self.classes[p, i, :len(labels)] = labels
+            self.optional[p, :len(opt)] = opt
+        self._device = {}
+
+    def __len__(self):
+        return len(self.names)
+
+    def __reduce__(self):
+        return (KeyedFieldSet, ({n: (list(k), p) for n, (k, p) in self.mapping.items()}, self.case_insensitive))
+
+    def tensors(self, device):
+        """(labels i32 [K, max_kw], alternatives i32 [K, max_kw] or None when case-sensitive, keyword
+        lengths i32 [K], groups i32 [K], classes i32 [n, max_len, 16], optional i32 [n, max_len], pattern
+        lengths i32 [n]) on `device`, uploaded once per device."""
+        key = str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            up = lambda a: torch.from_numpy(a).to(device)                    # noqa: E731
+            t = self._device[key] = (up(self.labels), up(self.alternatives) if self.case_insensitive else None,
+                                     up(self.kw_lengths), up(self.groups), up(self.classes), up(self.optional),
+                                     up(self.lengths))
+        return t
+
+    strings = FieldSet.strings
+
+
+def ctc_keyed_field_reader(inputs, sequence_length, keyed, gap_cost=0.0):
+    """For each keyed field of `keyed` (a KeyedFieldSet) and each row of inputs
+    [T, B, C], on the first sequence_length[b] frames: the jointly best placement
+    of one of the field's keywords, then a gap, then a string matching its
+    pattern (ocrk_ctc_keyed_field: the keyword / value pairing of
+    src/extract_fields/extractor.py, made on the lattice, where "the amount after
+    TOTAL" can still be told from "the amount after CASH"). gap_cost >= 0, nats
+    per frame between keyword and value: 0 leaves the gap free, a positive value
+    prefers the value nearest its keyword. Returns (score f32 [B, P]: <= 0, and 0
+    when the greedy path spells a keyword and later a matching string; kw_index
+    i32 [B, P]: into keyed.keywords; kw_score f32 [B, P]: the keyword placement's
+    own score; span i32 [B, P, 4]: (kw_first, kw_end, first, end) frames, for
+    frames_to_px; text i32 [B, P, max_len]: the label chosen at each position,
+    -1 for an absent one: keyed.strings turns it into strings). A field with no
+    keyword-then-value path in the row has -inf, -1, -inf, -1s and -1s. Device
+    tensors, no host sync."""
+    lab, alt, ln, grp, cls, opt, pln = keyed.tensors(inputs.device)
+    score, span, kw_index, kw_score, text, _ks, _ps = K.ctc_keyed_field(
+        _f32(inputs), sequence_length.to(torch.int32).contiguous(), lab, alt, ln, grp, cls, opt, pln, gap_cost)
+    return score, kw_index, kw_score, span, text
 
 
 # Where a frame sits in the crop (src/weinman/model.py:134-163), in input-column

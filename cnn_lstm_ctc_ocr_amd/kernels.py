@@ -1020,6 +1020,54 @@ def ctc_field(logits, seq_len, pat_cls, pat_opt, pat_len):
     return score, span, text, pat_status
 
 
+def ctc_keyed_field(logits, seq_len, kw, kw_alt, kw_len, kw_group, pat_cls, pat_opt, pat_len, gap_cost=0.0):
+    """The jointly best placement of a keyword of each keyed field's group, then a gap, then a
+    string matching the field's pattern, inside every row (ocrk_ctc_keyed_field).
+
+    logits f32 [T,B,C]; seq_len i32 [B]; kw, kw_alt (or None), kw_len as ctc_spot; kw_group i32 [K]:
+    the keyed field in [0, P) each keyword belongs to; pat_cls, pat_opt, pat_len as ctc_field, one
+    pattern per keyed field; gap_cost >= 0: nats per frame between the keyword and the field.
+    Returns (score f32 [B,P]: <= 0; span i32 [B,P,4]: (kw_first, kw_end, first, end) frames,
+    kw_first < kw_end <= first < end; kw_index i32 [B,P]: into the keyword list; kw_score f32 [B,P]:
+    the keyword placement's own score; text i32 [B,P,Wmax]: the label chosen per position, -1 for
+    an absent or unused one; kw_status i32 [K]; pat_status i32 [P]: ctc_spot's and ctc_field's codes,
+    3 for a kw_group outside [0, P)). A field with no keyword-then-string path in a row has -inf,
+    -1s, -1, -inf and -1s there and sets no status bit."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_keyed_field takes float32 logits")
+    if (kw.dim() != 2 or kw_len.dim() != 1 or kw_group.dim() != 1
+            or not kw.shape[0] == kw_len.shape[0] == kw_group.shape[0]):
+        raise ValueError("ctc_keyed_field takes kw [K, Wmax], kw_len [K] and kw_group [K]")
+    if kw_alt is not None and kw_alt.shape != kw.shape:
+        raise ValueError("ctc_keyed_field takes kw_alt of kw's shape")
+    if (pat_cls.dim() != 3 or pat_cls.shape[2] != 16 or pat_len.dim() != 1 or pat_cls.shape[0] != pat_len.shape[0]):
+        raise ValueError("ctc_keyed_field takes pat_cls [P, Wmax, 16] and pat_len [P]")
+    if pat_opt.shape != pat_cls.shape[:2]:
+        raise ValueError("ctc_keyed_field takes pat_opt [P, Wmax] beside pat_cls [P, Wmax, 16]")
+    ints = (kw, kw_len, kw_group, pat_cls, pat_opt, pat_len, seq_len) + (() if kw_alt is None else (kw_alt,))
+    if any(t.dtype != torch.int32 for t in ints):
+        raise TypeError("ctc_keyed_field takes int32 keyword, pattern and seq_len tensors")
+    _chk(logits, seq_len, kw, kw_alt, kw_len, kw_group, pat_cls, pat_opt, pat_len)
+    T, B, C = logits.shape
+    n_kw, Wkw = kw.shape
+    n_key, Wpat = pat_opt.shape
+    dev = logits.device
+    nb = _lib.lib().ocrk_ctc_keyed_field_workspace_size(T, B, C, n_kw, Wkw, n_key, Wpat)
+    ws = _ws(nb, dev)
+    score = torch.empty(B, n_key, dtype=torch.float32, device=dev)
+    span = torch.empty(B, n_key, 4, dtype=torch.int32, device=dev)
+    kw_index = torch.empty(B, n_key, dtype=torch.int32, device=dev)
+    kw_score = torch.empty(B, n_key, dtype=torch.float32, device=dev)
+    text = torch.empty(B, n_key, Wpat, dtype=torch.int32, device=dev)
+    kw_status = torch.empty(n_kw, dtype=torch.int32, device=dev)
+    pat_status = torch.empty(n_key, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_keyed_field", ptr(logits), ptr(seq_len), T, B, C, ptr(kw), ptr(kw_alt), ptr(kw_len), ptr(kw_group),
+         n_kw, Wkw, ptr(pat_cls), ptr(pat_opt), ptr(pat_len), n_key, Wpat, float(gap_cost), ptr(score), ptr(span),
+         ptr(kw_index), ptr(kw_score), ptr(text), ptr(kw_status), ptr(pat_status), ptr(status_word(dev)), ptr(ws), nb,
+         _stream(logits))
+    return score, span, kw_index, kw_score, text, kw_status, pat_status
+
+
 def ctc_greedy_decode(logits, seq_len, merge_repeated=True):
     """Greedy decode. Returns (out i64 [B,T] -1 padded, out_len i32 [B], neg_sum f32 [B])."""
     if logits.dtype != torch.float32:

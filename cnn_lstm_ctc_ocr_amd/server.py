@@ -130,6 +130,31 @@ def _field_threshold(value, who):
     return value
 
 
+def _keyed_set(keyed, case_insensitive, who):
+    """keyed_fields as a decode.KeyedFieldSet (or None): a KeyedFieldSet as it is, a mapping
+    name -> (keywords, pattern) encoded with case_insensitive."""
+    if keyed is None or isinstance(keyed, decode.KeyedFieldSet):
+        return keyed
+    if not isinstance(keyed, Mapping):
+        raise TypeError(f"{who}: keyed_fields is a decode.KeyedFieldSet or a mapping name -> (keywords, pattern), "
+                        f"not {type(keyed).__name__}")
+    return decode.KeyedFieldSet(keyed, case_insensitive)
+
+
+def _keyed_threshold(value, who):
+    value = float(value)
+    if not value <= 0:
+        raise ValueError(f"{who}: keyed_threshold is a log likelihood ratio, at most 0 (got {value})")
+    return value
+
+
+def _keyed_gap_cost(value, who):
+    value = float(value)
+    if not 0 <= value < math.inf:                            # NaN refused too
+        raise ValueError(f"{who}: keyed_gap_cost is in nats per frame, at least 0 and finite (got {value})")
+    return value
+
+
 class Recognition(NamedTuple):
     """What Recognizer(detail=True) returns per crop (a plain tuple of built-in
     values: it crosses ReplicaPool's and a Manager's queues pickled)."""
@@ -187,6 +212,32 @@ class FieldRecognition(NamedTuple):
     fields: Tuple[FieldHit, ...]                   # score >= field_threshold; best first, then by pattern order
 
 
+class KeyedHit(NamedTuple):
+    """One keyed field read out of a crop (Recognizer(keyed_fields=...)): built-in values only."""
+    name: str
+    keyword: str                                   # the keyword of the field's group the value was found after
+    text: str                                      # the best-scoring string matching the field's pattern after it
+    score: float                                   # ln p(best keyword-gap-value path) / p(greedy path there), <= 0
+    keyword_score: float                           # the keyword placement's own score, <= 0
+    kw_first_frame: int                            # the keyword's frames: first of its first symbol,
+    kw_end_frame: int                              # one past the last of its last symbol (<= first_frame)
+    kw_x0: float                                   # decode.frames_to_px(kw_first_frame, kw_end_frame, width)
+    kw_x1: float
+    first_frame: int                               # the value's frames
+    end_frame: int
+    x0: float                                      # decode.frames_to_px(first_frame, end_frame, width)
+    x1: float
+
+
+class KeyedRecognition(NamedTuple):
+    """What Recognizer(keyed_fields=...) returns per crop (built-in values only, like Recognition)."""
+    text: str                                      # the string the same recogniser returns without keyed_fields
+    detail: Optional[Recognition]                  # the Recognition with detail=True, else None
+    hits: Tuple[KeywordHit, ...]                   # as KeywordRecognition.hits when keywords are given too, else ()
+    fields: Tuple[FieldHit, ...]                   # as FieldRecognition.fields when fields are given too, else ()
+    keyed: Tuple[KeyedHit, ...]                    # score >= keyed_threshold; best first, then in field order
+
+
 class Recognizer:
     """The per-batch model step of LocalServer.run (server.py:80-89, 132-138):
     uint8 [bs, 32, W, 1] + widths -> one string per crop. Holds the variables
@@ -226,12 +277,23 @@ class Recognizer:
     (decode.ctc_field_reader on the same forward's logits) scores at least
     field_threshold (default ln 0.5), with its frames and pixel columns. One
     more entry call per batch (two launches), none without fields. Not
-    combined with lexicon."""
+    combined with lexicon.
+
+    keyed_fields (a decode.KeyedFieldSet or a mapping name -> (keywords,
+    pattern), then encoded with case_insensitive): a value read after its
+    keyword, "the amount after TOTAL". __call__ returns a KeyedRecognition per
+    crop: text, detail, hits and fields exactly as without keyed_fields (() for
+    what was not asked for), and a KeyedHit for every keyed field whose jointly
+    best keyword-gap-value placement (decode.ctc_keyed_field_reader on the same
+    forward's logits, with keyed_gap_cost nats per frame of gap) scores at
+    least keyed_threshold (default ln 0.5). One more entry call per batch (four
+    launches), none without keyed_fields. Not combined with lexicon."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
                  graphs=False, detail=False, lexicon=None, lexicon_top=1, keywords=None,
                  keyword_threshold=math.log(0.5), case_insensitive=False, fields=None,
-                 field_threshold=math.log(0.5)):
+                 field_threshold=math.log(0.5), keyed_fields=None, keyed_threshold=math.log(0.5),
+                 keyed_gap_cost=0.0):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -260,6 +322,11 @@ class Recognizer:
         if self.fields is not None and lexicon is not None:
             raise ValueError("Recognizer: fields and lexicon are two different questions; pass one of them")
         self.field_threshold = _field_threshold(field_threshold, "Recognizer")
+        self.keyed_fields = _keyed_set(keyed_fields, case_insensitive, "Recognizer")
+        if self.keyed_fields is not None and lexicon is not None:
+            raise ValueError("Recognizer: keyed_fields and lexicon are two different questions; pass one of them")
+        self.keyed_threshold = _keyed_threshold(keyed_threshold, "Recognizer")
+        self.keyed_gap_cost = _keyed_gap_cost(keyed_gap_cost, "Recognizer")
 
     def _graphed(self, batch, widths, decoded=True):
         """decoded=False: the forward alone (the lexicon path launches no unconstrained decoder)."""
@@ -450,7 +517,9 @@ class Recognizer:
         """One FieldRecognition per crop: what keyword_recognitions() (with keywords) or labels() /
         recognitions() give, and the field-reading launch on the same forward's logits (the replayed
         graph's, with graphs=True). A pattern that fits a crop's frames nowhere is never a hit."""
-        decoded = self._decoded(batch, widths)
+        return self._field_recognitions(self._decoded(batch, widths), widths)
+
+    def _field_recognitions(self, decoded, widths):
         logits, seq_len = decoded[0], decoded[1]
         with torch.no_grad():
             score, span, text = decode.ctc_field_reader(logits, seq_len, self.fields)
@@ -473,7 +542,45 @@ class Recognizer:
             found[b].append(FieldHit(names[p], w, s, f, e, a0, a1))
         return [FieldRecognition(t, d, h, tuple(f)) for (t, d, h), f in zip(base, found)]
 
+    def keyed_recognitions(self, batch, widths):
+        """One KeyedRecognition per crop: what field_recognitions() (with fields), keyword_recognitions()
+        (with keywords) or labels() / recognitions() give, and the keyed-field entry on the same forward's
+        logits (the replayed graph's, with graphs=True). A keyed field with no keyword-then-value path in
+        a crop's frames is never a hit."""
+        decoded = self._decoded(batch, widths)
+        logits, seq_len = decoded[0], decoded[1]
+        with torch.no_grad():
+            score, kw_index, kw_score, span, text = decode.ctc_keyed_field_reader(logits, seq_len, self.keyed_fields,
+                                                                                  self.keyed_gap_cost)
+        if self.fields is not None:
+            base = [(r.text, r.detail, r.hits, r.fields) for r in self._field_recognitions(decoded, widths)]
+        elif self.keywords is not None:
+            base = [(r.text, r.detail, r.hits, ()) for r in self._keyword_recognitions(*decoded, widths)]
+        else:
+            base = [(t, d, (), ()) for t, d in zip(*self._texts(*decoded, widths))]
+        score, kw_index, kw_score = score.cpu().numpy(), kw_index.cpu().numpy(), kw_score.cpu().numpy()
+        span, text = span.cpu().numpy(), text.cpu().numpy()
+        # whole-array host work on the hits alone: by crop, then score descending, then field order
+        bs, ps = np.nonzero((score >= self.keyed_threshold) & (span[:, :, 2] >= 0))
+        order = np.lexsort((ps, -score[bs, ps], bs))
+        bs, ps = bs[order], ps[order]
+        sp = span[bs, ps]
+        w = np.asarray(widths, np.float64)[bs]
+        k0, k1 = decode.frames_to_px(sp[:, 0], sp[:, 1], w)
+        x0, x1 = decode.frames_to_px(sp[:, 2], sp[:, 3], w)
+        strings = self.keyed_fields.strings(text[bs, ps]) if len(bs) else []
+        names, words = self.keyed_fields.names, self.keyed_fields.keywords
+        found = [[] for _ in base]
+        for b, p, k, t, s, ks, fr, a0, a1, c0, c1 in zip(
+                bs.tolist(), ps.tolist(), kw_index[bs, ps].tolist(), strings, score[bs, ps].tolist(),
+                kw_score[bs, ps].tolist(), sp.tolist(), np.atleast_1d(k0).tolist(), np.atleast_1d(k1).tolist(),
+                np.atleast_1d(x0).tolist(), np.atleast_1d(x1).tolist()):
+            found[b].append(KeyedHit(names[p], words[k], t, s, ks, fr[0], fr[1], a0, a1, fr[2], fr[3], c0, c1))
+        return [KeyedRecognition(t, d, h, f, tuple(k)) for (t, d, h, f), k in zip(base, found)]
+
     def __call__(self, batch, widths):
+        if self.keyed_fields is not None:
+            return self.keyed_recognitions(batch, widths)
         if self.fields is not None:
             return self.field_recognitions(batch, widths)
         if self.keywords is not None:
@@ -623,20 +730,23 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
 
 def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
                    detail=False, lexicon=None, lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5),
-                   case_insensitive=False, fields=None, field_threshold=math.log(0.5)):
+                   case_insensitive=False, fields=None, field_threshold=math.log(0.5), keyed_fields=None,
+                   keyed_threshold=math.log(0.5), keyed_gap_cost=0.0):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
     reference initialisers with `seed`). Picklable (spawn); a lexicon or a
     keyword list travels as its plain list of strings, field patterns as their plain
-    mapping, and they are encoded in the replica."""
+    mapping, keyed fields as their plain mapping too, and they are encoded in the replica."""
     return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top,
-                                 keywords, keyword_threshold, case_insensitive, fields, field_threshold)
+                                 keywords, keyword_threshold, case_insensitive, fields, field_threshold, keyed_fields,
+                                 keyed_threshold, keyed_gap_cost)
 
 
 class _GpuRecognizerFactory:
     def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False, lexicon=None,
                  lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5), case_insensitive=False,
-                 fields=None, field_threshold=math.log(0.5)):
+                 fields=None, field_threshold=math.log(0.5), keyed_fields=None, keyed_threshold=math.log(0.5),
+                 keyed_gap_cost=0.0):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
         self.allow_bf16, self.detail = allow_bf16, detail
         if lexicon is not None:                             # checked here, in the parent; pickled as strings
@@ -653,6 +763,13 @@ class _GpuRecognizerFactory:
             raise ValueError("gpu_recognizer: fields and lexicon are two different questions; pass one of them")
         self.fields = None if fset is None else dict(fset.patterns)
         self.field_threshold = _field_threshold(field_threshold, "gpu_recognizer")
+        kset = _keyed_set(keyed_fields, self.case_insensitive, "gpu_recognizer")   # pickled as a mapping
+        if kset is not None and lexicon is not None:
+            raise ValueError("gpu_recognizer: keyed_fields and lexicon are two different questions; pass one of them")
+        self.keyed_fields = None if kset is None else {n: (list(k), p) for n, (k, p) in kset.mapping.items()}
+        self.keyed_case_insensitive = self.case_insensitive if kset is None else kset.case_insensitive
+        self.keyed_threshold = _keyed_threshold(keyed_threshold, "gpu_recognizer")
+        self.keyed_gap_cost = _keyed_gap_cost(keyed_gap_cost, "gpu_recognizer")
 
     def __call__(self, device):
         from .config import ModelConfig
@@ -665,7 +782,10 @@ class _GpuRecognizerFactory:
                           detail=self.detail, lexicon=self.lexicon, lexicon_top=self.lexicon_top,
                           keywords=self.keywords, keyword_threshold=self.keyword_threshold,
                           case_insensitive=self.case_insensitive, fields=self.fields,
-                          field_threshold=self.field_threshold)
+                          field_threshold=self.field_threshold,
+                          keyed_fields=None if self.keyed_fields is None else decode.KeyedFieldSet(
+                              self.keyed_fields, self.keyed_case_insensitive),
+                          keyed_threshold=self.keyed_threshold, keyed_gap_cost=self.keyed_gap_cost)
 
 
 class ReplicaError(RuntimeError):

@@ -282,6 +282,70 @@ int ocrk_ctc_field(const float* logits, const int* seq_len, int T, int B, int C,
                    int* span, int* text, int* pat_status, uint32_t* status_word, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* Keyed field reading: for every row and every keyed field -- a group of keywords and one
+ * pattern -- the jointly best placement of one of the group's keywords, then a gap, then a string
+ * matching the pattern: "the amount after TOTAL" (added within v7; the reference's
+ * src/extract_fields/extractor.py pairs a keyword found by KWDetector.detect with the value
+ * KWExtractor.extract reads from the keyword's position onward, on the decoded line). On
+ * "TOTAL 12.50 CASH 20.00" ocrk_ctc_field returns whichever amount scores best and a join of its
+ * output with ocrk_ctc_spot's cannot recover the other one: the join is made on the lattice.
+ * L, rel, the keywords (labels, optional alternatives, 1..32 symbols) and the patterns (1..16
+ * positions) are ocrk_ctc_spot's and ocrk_ctc_field's, with their limits. The keywords come as
+ * one flat list with kw_group[k] in [0, n_key): the keyed field keyword k belongs to (a keyword
+ * wanted by two fields is listed twice); keyed field a has pattern a.
+ *   1. Keyword trail: ocrk_ctc_spot's recursion unchanged (same candidates, same order,
+ *      strictly-greater replacement, entry float32 0 at state 0). After frame t,
+ *      K_k[t] = (V[t][S-1], its start) is keyword k's best placement ending exactly at frame
+ *      t + 1: the value the spotter compares with its running best.
+ *   2. Gap state per (row, keyed field): G[t] is what a field entering position 0 at frame t
+ *      inherits. G[0] = (-inf, no keyword). For t >= 1 the candidates are, in this order, a later
+ *      one replacing the current only if strictly greater: the carry G[t-1].value - gap_cost, one
+ *      float32 subtraction, keeping its keyword index and keyword span, a candidate only when
+ *      G[t-1] has a keyword; then for each keyword k of the group, ascending k, K_k[t-1].value
+ *      with keyword index k and span (K_k[t-1].start, t). gap_cost >= 0 is in nats per frame
+ *      between the keyword's end and the field's first frame: with 0 the gap is the free greedy
+ *      filler of the other two entries, a positive value prefers the value nearest its keyword.
+ *   3. Field lattice: ocrk_ctc_field's recursion with one change: for position 0 the entry
+ *      candidate at frame t is G[t].value with start t instead of float32 0. The end-position
+ *      visit, its extension rule and what a state carries are unchanged.
+ *   4. Per (row, keyed field): score, the lattice's value, <= 0, and exactly 0 when the
+ *      frame-argmax path spells a keyword and later a matching string and gap_cost . gap is 0;
+ *      span (kw_first, kw_end, first, end) with the keyword's two read from G[first], so
+ *      kw_first < kw_end <= first < end <= L; kw_index into the flat keyword list; kw_score =
+ *      K_k[kw_end-1].value, the keyword placement's own value; text as in ocrk_ctc_field.
+ * Two things follow. Among equal scores the earliest-ending keyword and the earliest-ending field
+ * win: when the model reads the line exactly, the leftmost value after the leftmost keyword is
+ * returned, the reference's leftmost regex match. And keyword and field may abut
+ * (kw_end == first): no frame has to lie between them.
+ *   logits   f32 [T, B, C] (C <= 256, T <= 4096)     seq_len i32 [B]
+ *   kw, kw_alt (or NULL), kw_len: as ocrk_ctc_spot; kw_group i32 [n_kw]
+ *   pat_cls, pat_opt, pat_len: as ocrk_ctc_field, n_key patterns; 1 <= n_key <= 2^20
+ *   gap_cost f32 >= 0
+ *   score    f32 [B][n_key]          span     i32 [B][n_key][4], 16-B aligned
+ *   kw_index i32 [B][n_key]          kw_score f32 [B][n_key]
+ *   text     i32 [B][n_key][max_pat_len]
+ * No keyword-then-field path in L frames gives score -inf, span -1s, kw_index -1, kw_score -inf
+ * and text -1s, and sets no status bit: an ordinary result, as in the other two entries.
+ *   kw_status i32 [n_kw] or NULL, pat_status i32 [n_key] or NULL: ocrk_ctc_spot's and
+ *          ocrk_ctc_field's codes; a keyword whose kw_group is outside [0, n_key) has code 3.
+ *          Such a keyword is never scored, such a pattern's field gives -inf on every row, as
+ *          does a field whose group is empty or has no valid keyword; labels of invalid entries
+ *          are never used as indices; the OCRK_STATUS_CTC_BAD_LENGTH / _BAD_LABEL bits are
+ *          OR-ed into status_word (if given).
+ * A negative or NaN gap_cost, a null pointer, a workspace that is too small and sizes outside the
+ * two entries' limits return an error and launch nothing.
+ * No floating-point atomics: the whole call is reproducible bit for bit.
+ *   ws: >= ocrk_ctc_keyed_field_workspace_size(...) bytes, 16-B aligned (the rel table, a word per
+ *       keyword and per pattern, the trails f32x2 [B][n_kw][T], the gap states 16 B [B][n_key][T]). */
+size_t ocrk_ctc_keyed_field_workspace_size(int T, int B, int C, int n_kw, int max_kw_len, int n_key,
+                                           int max_pat_len);
+int ocrk_ctc_keyed_field(const float* logits, const int* seq_len, int T, int B, int C, const int* kw,
+                         const int* kw_alt, const int* kw_len, const int* kw_group, int n_kw,
+                         int max_kw_len, const int* pat_cls, const int* pat_opt, const int* pat_len,
+                         int n_key, int max_pat_len, float gap_cost, float* score, int* span,
+                         int* kw_index, float* kw_score, int* text, int* kw_status, int* pat_status,
+                         uint32_t* status_word, void* ws, size_t ws_bytes, void* stream);
+
 /* a10 -- validate._get_output (src/weinman/validate.py:81-92) =
  * tf.nn.ctc_greedy_decoder(logits, seq_len, merge_repeated) + sparse_to_dense(-1):
  *   out i64 [B, T] (labels then -1), out_len i32 [B], neg_sum_logits f32 [B] or NULL. */
