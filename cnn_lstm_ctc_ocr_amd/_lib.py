@@ -50,6 +50,9 @@ SIGNATURES = {
                                _p],
     "ocrk_ctc_spot_workspace_size": [_i32, _i32, _i32, _i32, _i32],
     "ocrk_ctc_spot": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _sz, _p],
+    "ocrk_ctc_spot_fuzzy_workspace_size": [_i32, _i32, _i32, _i32, _i32],
+    "ocrk_ctc_spot_fuzzy": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _i32, _i32, _f32, _p, _p, _p, _p, _p, _p, _sz,
+                            _p],
     "ocrk_ctc_field_workspace_size": [_i32, _i32, _i32, _i32, _i32],
     "ocrk_ctc_field": [_p, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _sz, _p],
     "ocrk_ctc_keyed_field_workspace_size": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],

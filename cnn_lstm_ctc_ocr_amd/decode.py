@@ -12,6 +12,9 @@ against the logits (what src/extract_fields and src/accuracy_measure do on the
 host with fuzzy matches of the decoded string), for server.LexiconRecognition.
 KeywordSet / ctc_keyword_spotter find keywords inside a line on the same logits
 (src/extract_fields/extractor.py's fuzzy regexes), for server.KeywordRecognition.
+FuzzyKeywordSet / ctc_fuzzy_keyword_spotter find them with up to two edits each
+(extractor.py's FuzzyRegexExtractor(maxerr=(len + 1) / 5)), for
+server.FuzzyKeywordHit.
 FieldSet / ctc_field_reader read the best string matching a small character-class
 pattern out of a line on the same logits (extractor.py's amount, GST and receipt
 number regexes over the 1-best string), for server.FieldRecognition.
@@ -238,7 +241,83 @@ def ctc_keyword_spotter(inputs, sequence_length, keywords):
     return score, span
 
 
-_FIELD_SPECIAL = "\\[]{}?.*+()|^$"                          # literals only when escaped
+MAX_KEYWORD_ERRORS = 2                                      # ocrk_ctc_spot_fuzzy: layers of the lattice in registers
+
+
+class FuzzyKeywordSet(KeywordSet):
+    """A KeywordSet whose keywords may be found with edits: max_errors is the
+    number of substituted, inserted or deleted symbols allowed per keyword, one
+    int for all, one per keyword, or "auto": min(2, (len + 1) // 5), the
+    reference's FuzzyRegexExtractor(maxerr=(len + 1) / 5) capped at the
+    kernel's two. ValueError for a budget outside 0..min(2, len - 1) (and
+    KeywordSet's own). Pickles as its arguments."""
+
+    def __init__(self, keywords, max_errors="auto", case_insensitive=False):
+        super().__init__(keywords, case_insensitive)
+        lengths = [int(n) for n in self.lengths]
+        if isinstance(max_errors, str):
+            if max_errors != "auto":
+                raise ValueError(f"FuzzyKeywordSet: max_errors is 'auto', an int or one int per keyword, "
+                                 f"not {max_errors!r}")
+            budgets = [min(MAX_KEYWORD_ERRORS, (n + 1) // 5) for n in lengths]
+        elif isinstance(max_errors, (int, np.integer)) and not isinstance(max_errors, bool):
+            budgets = [int(max_errors)] * len(lengths)
+        else:
+            try:
+                budgets = list(max_errors)
+            except TypeError:
+                raise ValueError(f"FuzzyKeywordSet: max_errors is 'auto', an int or one int per keyword, "
+                                 f"not {type(max_errors).__name__}") from None
+            if len(budgets) != len(lengths):
+                raise ValueError(f"FuzzyKeywordSet: {len(budgets)} budgets for {len(lengths)} keywords")
+            for i, e in enumerate(budgets):
+                if isinstance(e, bool) or not isinstance(e, (int, np.integer)):
+                    raise ValueError(f"FuzzyKeywordSet: the budget of entry {i} is {type(e).__name__}, not an int")
+            budgets = [int(e) for e in budgets]
+        for i, (e, n) in enumerate(zip(budgets, lengths)):
+            if not 0 <= e <= min(MAX_KEYWORD_ERRORS, n - 1):
+                raise ValueError(f"FuzzyKeywordSet: {self.keywords[i]!r} (entry {i}) takes 0.."
+                                 f"{min(MAX_KEYWORD_ERRORS, n - 1)} errors, not {e}")
+        self.max_errors = max_errors if isinstance(max_errors, str) else tuple(budgets)
+        self.errors = np.array(budgets, np.int32)
+
+    def __reduce__(self):
+        arg = self.max_errors if isinstance(self.max_errors, str) else list(self.max_errors)
+        return (FuzzyKeywordSet, (list(self.keywords), arg, self.case_insensitive))
+
+    def fuzzy_tensors(self, device):
+        """KeywordSet.tensors(device) and the budgets i32 [n] on `device`, uploaded once per device."""
+        key = "errors:" + str(torch.device(device))
+        t = self._device.get(key)
+        if t is None:
+            t = self._device[key] = torch.from_numpy(self.errors).to(device)
+        return self.tensors(device) + (t,)
+
+
+def ctc_fuzzy_keyword_spotter(inputs, sequence_length, keywords, edit_cost=0.0):
+    """ctc_keyword_spotter with edits: where each keyword of `keywords` (a
+    FuzzyKeywordSet) reads best inside each row of inputs [T, B, C] when up to
+    its budget of symbols may be substituted, inserted or (inside the keyword)
+    deleted (ocrk_ctc_spot_fuzzy; src/extract_fields/extractor.py's
+    FuzzyRegexExtractor, on the lattice instead of the decoded string). A
+    substituted or inserted symbol reads as the frames' best non-blank class
+    and costs nothing beyond edit_cost (>= 0, a log likelihood ratio charged
+    once per edit). Returns (score f32 [B, K], <= 0 and 0 when the greedy path
+    spells the keyword within its budget and edit_cost is 0; span i32 [B, K, 2];
+    errors i32 [B, K]: the edits the best path used, -1 with -inf and (-1, -1)
+    where there is no path). Device tensors, no host sync."""
+    if not isinstance(keywords, FuzzyKeywordSet):
+        raise TypeError(f"ctc_fuzzy_keyword_spotter takes a FuzzyKeywordSet, not {type(keywords).__name__}")
+    edit_cost = float(edit_cost)
+    if not edit_cost >= 0:
+        raise ValueError(f"ctc_fuzzy_keyword_spotter: edit_cost is at least 0 (got {edit_cost})")
+    lab, alt, ln, err = keywords.fuzzy_tensors(inputs.device)
+    score, span, errors, _status = K.ctc_spot_fuzzy(_f32(inputs), sequence_length.to(torch.int32).contiguous(), lab,
+                                                    alt, ln, err, edit_cost)
+    return score, span, errors
+
+
+_FIELD_SPECIAL ="\\[]{}?.*+()|^$"                          # literals only when escaped
 _FIELD_UNSUPPORTED = ".*+()|^$"                             # what a regular expression has and a field pattern lacks
 
 

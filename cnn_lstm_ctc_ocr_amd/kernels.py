@@ -984,6 +984,39 @@ def ctc_spot(logits, seq_len, kw, kw_alt, kw_len):
     return score, span, kw_status
 
 
+def ctc_spot_fuzzy(logits, seq_len, kw, kw_alt, kw_len, kw_err, edit_cost=0.0):
+    """The best path inside every row that spells every keyword with at most kw_err[k] <= 2 edits,
+    scored against the greedy path (ocrk_ctc_spot_fuzzy).
+
+    logits, seq_len, kw, kw_alt (or None), kw_len as ctc_spot; kw_err i32 [K]: the edits allowed,
+    0..min(2, kw_len - 1); edit_cost: a float >= 0 (inf allowed) subtracted once per edit.
+    Returns (score f32 [B,K], span i32 [B,K,2], errors i32 [B,K]: the edits the best path used, -1
+    with -inf and (-1, -1) where there is no path; kw_status i32 [K]: ctc_spot's codes, 2 also for
+    a budget out of range)."""
+    if logits.dtype != torch.float32:
+        raise TypeError("ctc_spot_fuzzy takes float32 logits")
+    if kw.dim() != 2 or kw_len.dim() != 1 or kw.shape[0] != kw_len.shape[0] or kw_err.shape != kw_len.shape:
+        raise ValueError("ctc_spot_fuzzy takes kw [K, Wmax], kw_len [K] and kw_err [K]")
+    if kw_alt is not None and kw_alt.shape != kw.shape:
+        raise ValueError("ctc_spot_fuzzy takes kw_alt of kw's shape")
+    if any(t.dtype != torch.int32 for t in (kw, kw_len, kw_err, seq_len) + (() if kw_alt is None else (kw_alt,))):
+        raise TypeError("ctc_spot_fuzzy takes int32 kw, kw_alt, kw_len, kw_err and seq_len")
+    _chk(logits, seq_len, kw, kw_alt, kw_len, kw_err)
+    T, B, C = logits.shape
+    n_kw, Wmax = kw.shape
+    dev = logits.device
+    nb = _lib.lib().ocrk_ctc_spot_fuzzy_workspace_size(T, B, C, n_kw, Wmax)
+    ws = _ws(nb, dev)
+    score = torch.empty(B, n_kw, dtype=torch.float32, device=dev)
+    span = torch.empty(B, n_kw, 2, dtype=torch.int32, device=dev)
+    errors = torch.empty(B, n_kw, dtype=torch.int32, device=dev)
+    kw_status = torch.empty(n_kw, dtype=torch.int32, device=dev)
+    call("ocrk_ctc_spot_fuzzy", ptr(logits), ptr(seq_len), T, B, C, ptr(kw), ptr(kw_alt), ptr(kw_len), ptr(kw_err),
+         n_kw, Wmax, float(edit_cost), ptr(score), ptr(span), ptr(errors), ptr(kw_status), ptr(status_word(dev)),
+         ptr(ws), nb, _stream(logits))
+    return score, span, errors, kw_status
+
+
 def ctc_field(logits, seq_len, pat_cls, pat_opt, pat_len):
     """The best-scoring string matching every character-class pattern inside every row, scored
     against the greedy path (ocrk_ctc_field).

@@ -106,6 +106,27 @@ def _keyword_set(keywords, case_insensitive, who):
     return decode.KeywordSet(keywords, case_insensitive)
 
 
+def _fuzzy_keyword_set(keywords, errors, who):
+    """The keyword set of keywords= with keyword_errors=: without keyword_errors the set as it is (a
+    decode.FuzzyKeywordSet keeps its own budgets); with them a decode.FuzzyKeywordSet of the same keywords."""
+    if errors is None:
+        return keywords
+    if keywords is None:
+        raise ValueError(f"{who}: keyword_errors needs keywords")
+    if isinstance(keywords, decode.FuzzyKeywordSet):
+        raise ValueError(f"{who}: the decode.FuzzyKeywordSet has its budgets already; leave keyword_errors out")
+    return decode.FuzzyKeywordSet(list(keywords.keywords), errors, keywords.case_insensitive)
+
+
+def _keyword_edit_cost(value, fuzzy, who):
+    value = float(value)
+    if not value >= 0:                                       # NaN refused too; +inf allows no edit at all
+        raise ValueError(f"{who}: keyword_edit_cost is a log likelihood ratio per edit, at least 0 (got {value})")
+    if value and not fuzzy:
+        raise ValueError(f"{who}: keyword_edit_cost needs keyword_errors or a decode.FuzzyKeywordSet")
+    return value
+
+
 def _keyword_threshold(value, who):
     value = float(value)
     if not value <= 0:                                       # a score is a log likelihood ratio <= 0 (NaN refused too)
@@ -184,6 +205,18 @@ class KeywordHit(NamedTuple):
     end_frame: int                                 # one past the last frame of the last symbol
     x0: float                                      # decode.frames_to_px(first_frame, end_frame, width)
     x1: float
+
+
+class FuzzyKeywordHit(NamedTuple):
+    """One keyword found inside a crop with edits allowed (Recognizer(keywords=..., keyword_errors=...)):
+    KeywordHit's fields, then the edits of the best path. Built-in values only."""
+    keyword: str
+    score: float                                   # ln p(best path spelling it within its budget) / p(greedy path)
+    first_frame: int
+    end_frame: int
+    x0: float
+    x1: float
+    errors: int                                    # substituted, inserted or deleted symbols of that path
 
 
 class KeywordRecognition(NamedTuple):
@@ -270,6 +303,16 @@ class Recognizer:
     and pixel columns. One more entry call per batch (two launches), none
     without keywords. Not combined with lexicon.
 
+    keyword_errors ("auto", an int or one int per keyword; or keywords given
+    as a decode.FuzzyKeywordSet): the keywords are found with up to that many
+    substituted, inserted or deleted symbols each, keyword_edit_cost (>= 0)
+    off the score per edit (decode.ctc_fuzzy_keyword_spotter in place of the
+    exact spotter: the same number of launches). The hits of
+    KeywordRecognition, FieldRecognition and KeyedRecognition are then
+    FuzzyKeywordHit, KeywordHit's fields plus errors, ordered by score
+    descending, then errors ascending, then keyword index. The keywords of
+    keyed_fields stay exact.
+
     fields (a decode.FieldSet or a mapping name -> pattern): field reading
     inside the line. __call__ returns a FieldRecognition per crop: text and
     detail exactly as without fields, hits as with keywords alone (() without
@@ -293,7 +336,7 @@ class Recognizer:
                  graphs=False, detail=False, lexicon=None, lexicon_top=1, keywords=None,
                  keyword_threshold=math.log(0.5), case_insensitive=False, fields=None,
                  field_threshold=math.log(0.5), keyed_fields=None, keyed_threshold=math.log(0.5),
-                 keyed_gap_cost=0.0):
+                 keyed_gap_cost=0.0, keyword_errors=None, keyword_edit_cost=0.0):
         if decoder not in ("greedy", "beam"):
             raise ValueError("decoder is 'greedy' or 'beam'")
         if store.cfg.dtype != torch.float32 and not allow_bf16:
@@ -314,7 +357,10 @@ class Recognizer:
             raise ValueError("Recognizer: lexicon_top is 1..32")
         self.lexicon = lexicon
         self.lexicon_top = int(lexicon_top)
-        self.keywords = _keyword_set(keywords, case_insensitive, "Recognizer")
+        self.keywords = _fuzzy_keyword_set(_keyword_set(keywords, case_insensitive, "Recognizer"), keyword_errors,
+                                           "Recognizer")
+        self.fuzzy_keywords = isinstance(self.keywords, decode.FuzzyKeywordSet)
+        self.keyword_edit_cost = _keyword_edit_cost(keyword_edit_cost, self.fuzzy_keywords, "Recognizer")
         if self.keywords is not None and lexicon is not None:
             raise ValueError("Recognizer: keywords and lexicon are two different questions; pass one of them")
         self.keyword_threshold = _keyword_threshold(keyword_threshold, "Recognizer")
@@ -496,6 +542,8 @@ class Recognizer:
         return [validate._get_string(row[:n]) for row, n in zip(rows, lens)], [None] * len(widths)
 
     def _keyword_recognitions(self, logits, seq_len, out, out_len, widths):
+        if self.fuzzy_keywords:
+            return self._fuzzy_keyword_recognitions(logits, seq_len, out, out_len, widths)
         with torch.no_grad():
             score, span = decode.ctc_keyword_spotter(logits, seq_len, self.keywords)
         texts, details = self._texts(logits, seq_len, out, out_len, widths)
@@ -511,6 +559,27 @@ class Recognizer:
         for b, k, s, f, e, a0, a1 in zip(bs.tolist(), ks.tolist(), score[bs, ks].tolist(), first.tolist(),
                                          end.tolist(), np.atleast_1d(x0).tolist(), np.atleast_1d(x1).tolist()):
             hits[b].append(KeywordHit(words[k], s, f, e, a0, a1))
+        return [KeywordRecognition(text, d, tuple(h)) for text, d, h in zip(texts, details, hits)]
+
+    def _fuzzy_keyword_recognitions(self, logits, seq_len, out, out_len, widths):
+        """_keyword_recognitions with the error-tolerant spotter: FuzzyKeywordHits, by score descending, then
+        errors ascending, then keyword index."""
+        with torch.no_grad():
+            score, span, errors = decode.ctc_fuzzy_keyword_spotter(logits, seq_len, self.keywords,
+                                                                   self.keyword_edit_cost)
+        texts, details = self._texts(logits, seq_len, out, out_len, widths)
+        score, span, errors = score.cpu().numpy(), span.cpu().numpy(), errors.cpu().numpy()
+        bs, ks = np.nonzero((score >= self.keyword_threshold) & (span[:, :, 0] >= 0))
+        order = np.lexsort((ks, errors[bs, ks], -score[bs, ks], bs))
+        bs, ks = bs[order], ks[order]
+        first, end = span[bs, ks, 0], span[bs, ks, 1]
+        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        words = self.keywords.keywords
+        hits = [[] for _ in texts]
+        for b, k, s, f, e, a0, a1, n in zip(bs.tolist(), ks.tolist(), score[bs, ks].tolist(), first.tolist(),
+                                            end.tolist(), np.atleast_1d(x0).tolist(), np.atleast_1d(x1).tolist(),
+                                            errors[bs, ks].tolist()):
+            hits[b].append(FuzzyKeywordHit(words[k], s, f, e, a0, a1, n))
         return [KeywordRecognition(text, d, tuple(h)) for text, d, h in zip(texts, details, hits)]
 
     def field_recognitions(self, batch, widths):
@@ -731,7 +800,7 @@ def _replica_main(rank, device, make_recognizer, inq, outq):
 def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_width=16, allow_bf16=False,
                    detail=False, lexicon=None, lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5),
                    case_insensitive=False, fields=None, field_threshold=math.log(0.5), keyed_fields=None,
-                   keyed_threshold=math.log(0.5), keyed_gap_cost=0.0):
+                   keyed_threshold=math.log(0.5), keyed_gap_cost=0.0, keyword_errors=None, keyword_edit_cost=0.0):
     """A make_recognizer for ReplicaPool: a Recognizer whose ParamStore is
     built on the replica's device (restored from a TF1 checkpoint, or the
     reference initialisers with `seed`). Picklable (spawn); a lexicon or a
@@ -739,20 +808,24 @@ def gpu_recognizer(cfg=None, checkpoint=None, seed=0, decoder="greedy", beam_wid
     mapping, keyed fields as their plain mapping too, and they are encoded in the replica."""
     return _GpuRecognizerFactory(cfg, checkpoint, seed, decoder, beam_width, allow_bf16, detail, lexicon, lexicon_top,
                                  keywords, keyword_threshold, case_insensitive, fields, field_threshold, keyed_fields,
-                                 keyed_threshold, keyed_gap_cost)
+                                 keyed_threshold, keyed_gap_cost, keyword_errors, keyword_edit_cost)
 
 
 class _GpuRecognizerFactory:
     def __init__(self, cfg, checkpoint, seed, decoder, beam_width, allow_bf16=False, detail=False, lexicon=None,
                  lexicon_top=1, keywords=None, keyword_threshold=math.log(0.5), case_insensitive=False,
                  fields=None, field_threshold=math.log(0.5), keyed_fields=None, keyed_threshold=math.log(0.5),
-                 keyed_gap_cost=0.0):
+                 keyed_gap_cost=0.0, keyword_errors=None, keyword_edit_cost=0.0):
         self.cfg, self.checkpoint, self.seed, self.decoder, self.beam_width = cfg, checkpoint, seed, decoder, beam_width
         self.allow_bf16, self.detail = allow_bf16, detail
         if lexicon is not None:                             # checked here, in the parent; pickled as strings
             lexicon = list(decode.Lexicon(lexicon).words if not isinstance(lexicon, decode.Lexicon) else lexicon.words)
         self.lexicon, self.lexicon_top = lexicon, lexicon_top
-        kws = _keyword_set(keywords, case_insensitive, "gpu_recognizer")     # checked here too; pickled as strings
+        kws = _fuzzy_keyword_set(_keyword_set(keywords, case_insensitive, "gpu_recognizer"), keyword_errors,
+                                 "gpu_recognizer")                           # checked here too; pickled as strings
+        fuzzy = isinstance(kws, decode.FuzzyKeywordSet)                      # and as its budgets
+        self.keyword_errors = [int(e) for e in kws.errors] if fuzzy else None
+        self.keyword_edit_cost = _keyword_edit_cost(keyword_edit_cost, fuzzy, "gpu_recognizer")
         if kws is not None and lexicon is not None:
             raise ValueError("gpu_recognizer: keywords and lexicon are two different questions; pass one of them")
         self.keywords = None if kws is None else list(kws.keywords)
@@ -785,7 +858,8 @@ class _GpuRecognizerFactory:
                           field_threshold=self.field_threshold,
                           keyed_fields=None if self.keyed_fields is None else decode.KeyedFieldSet(
                               self.keyed_fields, self.keyed_case_insensitive),
-                          keyed_threshold=self.keyed_threshold, keyed_gap_cost=self.keyed_gap_cost)
+                          keyed_threshold=self.keyed_threshold, keyed_gap_cost=self.keyed_gap_cost,
+                          keyword_errors=self.keyword_errors, keyword_edit_cost=self.keyword_edit_cost)
 
 
 class ReplicaError(RuntimeError):

@@ -224,6 +224,58 @@ int ocrk_ctc_spot(const float* logits, const int* seq_len, int T, int B, int C, 
                   int* span, int* kw_status, uint32_t* status_word, void* ws, size_t ws_bytes,
                   void* stream);
 
+/* Error-tolerant keyword spotting: ocrk_ctc_spot with up to two edits per keyword -- the best
+ * path inside the row that spells the keyword with at most err[k] substituted, inserted or
+ * deleted symbols, the number of edits it used and its frames (added within v7; the reference's
+ * src/extract_fields/extractor.py builds FuzzyRegexExtractor(reg, maxerr=(len+1)/5) per keyword
+ * and matches the decoded string on the host).
+ * L, rel, the keyword's S = 2 n - 1 states, its sets set(i) = {l_i, a_i} and the emission e[t][s]
+ * are ocrk_ctc_spot's. Per frame nb(t) = max over the non-blank classes c of rel[t][c], and a(t)
+ * is the lowest class that attains it. Per keyword a budget err[k] in {0, 1, 2}, err[k] <=
+ * kw_len[k] - 1. edit_cost >= 0 (float32, +inf allowed) is charged by one float32 subtraction on
+ * every edit transition, never multiplied.
+ * States: layers e = 0..err[k]; each holds the chain M[e][s] with emission e[t][s] and, for
+ * e >= 1, a wild state W[e][s] on every lane with emission nb(t): on an even lane it stands in
+ * place of symbol i = s/2 (a substitution), on an odd lane it is one extra symbol between i and
+ * i + 1 (an insertion). Every state carries the start frame of its path. V = best + emission,
+ * one float32 add; best is taken among the candidates below in the order listed, a later one
+ * replacing the current one only if strictly greater (all values are frame t - 1's).
+ * M[e][s]:  1. M[e][s];  2. M[e][s-1];  3. M[e][s-2], even s >= 2 with set(i), set(i-1) disjoint;
+ *   4. float32 0 with start t, only s = 0 and e = 0;  and for e >= 1:
+ *   5. W[e][s], odd s;  6. W[e][s-1], s >= 1: on odd s always, on even s only if a(t-1) is not in
+ *   set(i);  7. W[e][s-2], even s >= 2, only if a(t-1) is not in set(i);
+ *   8. M[e-1][s-3] - edit_cost, even s >= 4 (symbol i-1 deleted after a blank);
+ *   9. M[e-1][s-4] - edit_cost, even s >= 4 with set(i), set(i-2) disjoint.
+ * W[e][s], e >= 1:  1. W[e][s], only if t >= 1 and a(t) == a(t-1) (else -inf, start -1);
+ *   2. M[e-1][s] - edit_cost, odd s;  3. M[e-1][s-1] - edit_cost, s >= 1: on even s always, on
+ *   odd s only if a(t) is not in set((s-1)/2);  4. M[e-1][s-2] - edit_cost, even s >= 2, only if
+ *   a(t) is not in set(i-1);  5. 0 - edit_cost with start t, only s = 0 and e = 1;
+ *   6. W[1][s-1] - edit_cost, only e = 2, s >= 1, t >= 1 and a(t) != a(t-1).
+ * After each frame, for e ascending, M[e][S-1] and then W[e][S-1] (with start, t + 1 and e)
+ * replace the row's best only if strictly greater: among equal scores the earliest end, then the
+ * fewest edits, then a matched last symbol. A wild run is exactly one character (a run of frames
+ * with a constant best non-blank class) and the a() conditions keep it from touching a neighbour
+ * of the same class without a blank, so the CTC collapse of the path's frame labelling is within
+ * `errors` Levenshtein edits of a spelling of the keyword. Left out on purpose: the first and
+ * the last symbol can be substituted but not deleted (with a free start and end that is a
+ * shorter keyword), and a deletion starts from a matched state, so two adjacent deletions do not
+ * compose. With every budget 0, or with edit_cost = +inf, score and span are ocrk_ctc_spot's
+ * bytes.
+ *   logits, seq_len, kw, kw_alt (or NULL), kw_len, score, span, status_word: as ocrk_ctc_spot
+ *   kw_err i32 [n_kw]            edit_cost f32, >= 0 (a negative or NaN cost is refused)
+ *   errors i32 [B][n_kw]: the edits of the best path, 0..kw_err[k]; -1 with score -inf and span
+ *          (-1, -1) where no path exists (no status bit: an ordinary result)
+ *   kw_status i32 [n_kw] or NULL: ocrk_ctc_spot's codes, and 2 also for a budget outside
+ *          [0, min(2, kw_len - 1)]; such a keyword scores -inf, (-1, -1), -1 on every row.
+ * No floating-point atomics: the whole call is reproducible bit for bit.
+ *   ws: >= ocrk_ctc_spot_fuzzy_workspace_size(T, B, C, n_kw, max_kw_len) bytes, 16-B aligned (the
+ *       rel table, (nb, a) per frame, a word per keyword). */
+size_t ocrk_ctc_spot_fuzzy_workspace_size(int T, int B, int C, int n_kw, int max_kw_len);
+int ocrk_ctc_spot_fuzzy(const float* logits, const int* seq_len, int T, int B, int C, const int* kw,
+                        const int* kw_alt, const int* kw_len, const int* kw_err, int n_kw,
+                        int max_kw_len, float edit_cost, float* score, int* span, int* errors,
+                        int* kw_status, uint32_t* status_word, void* ws, size_t ws_bytes, void* stream);
+
 /* Field reading: the best-scoring string that matches a small character-class pattern, placed
  * anywhere inside a row, as a likelihood ratio against the greedy path, with the frames of the
  * hit and the label chosen at each position (added within v7; no reference graph op: the
