@@ -23,6 +23,7 @@ OCRK_ERR_INFEASIBLE = 3
 
 F32 = 0
 BF16 = 1
+U8 = 2           # page images only (ocrk_page_*)
 
 _p = ctypes.c_void_p
 _i32 = ctypes.c_int
@@ -157,6 +158,8 @@ SIGNATURES = {
     "ocrk_mul_scalar": [_p, _i64, _p, _p],
     "ocrk_mean": [_p, _i32, _p, _p],
     "ocrk_seq_len": [_p, _i32, _p, _p],
+    "ocrk_page_minmax": [_p, _i32, _i64, _p, _p, _p],
+    "ocrk_page_crops": [_p, _i32, _i32, _i32, _p, _p, _i32, _p, _i64, _p, _f32, _p],
     "ocrk_timer_create": [_p],
     "ocrk_timer_record": [_p, _p],
     "ocrk_timer_elapsed": [_p, _p, _p],

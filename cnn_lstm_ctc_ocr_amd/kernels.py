@@ -1152,3 +1152,49 @@ def edit_distance(hyp, hyp_len, labels, label_len, totals=None):
     call("ocrk_edit_distance", ptr(hyp), ptr(hyp_len), hyp.shape[1], ptr(labels), ptr(label_len),
          labels.shape[1], B, ptr(dist), ptr(totals) if totals is not None else None, _stream(hyp))
     return dist
+
+
+# ---------------------------------------------------------------- page -> crops
+def _page_dtype(page, who):
+    if page.dim() != 2 or page.numel() == 0:
+        raise ValueError(f"{who} takes a page [H, W] with at least one pixel")
+    if page.dtype == torch.uint8:
+        return _lib.U8
+    if page.dtype == torch.float32:
+        return _lib.F32
+    raise TypeError(f"{who} takes a uint8 or float32 page, not {page.dtype}")
+
+
+def page_minmax(page):
+    """(min, max) of a uint8 or float32 page [H, W] as f32 [2] on the device (ocrk_page_minmax):
+    one launch, no host sync."""
+    code = _page_dtype(page, "page_minmax")
+    _chk(page)
+    out = torch.empty(2, dtype=torch.float32, device=page.device)
+    ws = _ws(16, page.device)
+    call("ocrk_page_minmax", ptr(page), code, page.numel(), ptr(out), ptr(ws), _stream(page))
+    return out
+
+
+def page_crops(page, jobs, jobs_host, arena, minmax=None, scale=1.0):
+    """Every crop of a page in one launch (ocrk_page_crops).
+
+    page u8 / f32 [H, W]; jobs i32 [n, 8] on the device and jobs_host, the same table as a
+    contiguous int32 NumPy array (rows {y0, x0, h, w, nw, Wb, offset / 32, box}; the entry
+    validates it before launching); arena u8 [bytes], every job's span of it written;
+    minmax f32 [2] (page_minmax's) or None; scale: the gain's numerator (include/ocrk.h)."""
+    code = _page_dtype(page, "page_crops")
+    if jobs.dtype != torch.int32 or jobs.dim() != 2 or jobs.shape[1] != 8:
+        raise TypeError("page_crops takes int32 jobs [n, 8]")
+    if str(jobs_host.dtype) != "int32" or tuple(jobs_host.shape) != tuple(jobs.shape) \
+            or not jobs_host.flags["C_CONTIGUOUS"]:
+        raise TypeError("page_crops takes jobs_host as the contiguous int32 NumPy mirror of jobs")
+    if arena.dtype != torch.uint8 or arena.dim() != 1:
+        raise TypeError("page_crops takes a flat uint8 arena")
+    if minmax is not None and (minmax.dtype != torch.float32 or minmax.numel() != 2):
+        raise TypeError("page_crops takes minmax f32 [2]")
+    _chk(page, jobs, arena, minmax)
+    H, W = page.shape
+    call("ocrk_page_crops", ptr(page), code, H, W, ptr(jobs), ctypes.c_void_p(jobs_host.ctypes.data), jobs.shape[0],
+         ptr(arena), arena.numel(), ptr(minmax), float(scale), _stream(page))
+    return arena

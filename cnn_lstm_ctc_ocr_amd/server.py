@@ -176,6 +176,44 @@ def _keyed_gap_cost(value, who):
     return value
 
 
+def _checked_batch(batch):
+    if batch.dtype != torch.uint8 or batch.dim() != 4:
+        raise TypeError(f"Recognizer: a batch tensor is uint8 [bs, 32, W, 1], not {batch.dtype} {list(batch.shape)}")
+    return batch
+
+
+def _checked_widths(widths):
+    if widths.dtype != torch.int32 or widths.dim() != 1:
+        raise TypeError(f"Recognizer: a widths tensor is int32 [bs], not {widths.dtype} {list(widths.shape)}")
+    return widths
+
+
+def _device_batch(batch, dev):
+    """The batch on the recogniser's device: a tensor (page.page_crops's views) as it is, NumPy uploaded."""
+    if isinstance(batch, torch.Tensor):
+        return _checked_batch(batch).to(dev, non_blocking=True).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
+
+
+def _device_widths(widths, dev):
+    if isinstance(widths, torch.Tensor):
+        return _checked_widths(widths).to(dev, non_blocking=True).contiguous()
+    return torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+
+
+def _host_widths(widths):
+    """widths as float64 NumPy for the pixel extents of results that are read back anyway."""
+    if isinstance(widths, torch.Tensor):
+        widths = widths.cpu().numpy()
+    return np.asarray(widths, np.float64)
+
+
+class PageLines(NamedTuple):
+    """What Recognizer.page returns."""
+    results: list                                  # per box what __call__ returns for its crop; None if skipped
+    skipped: list                                  # page.PagePlan.skipped: (box index, "empty" | "narrow" | "wide")
+
+
 class Recognition(NamedTuple):
     """What Recognizer(detail=True) returns per crop (a plain tuple of built-in
     values: it crosses ReplicaPool's and a Manager's queues pickled)."""
@@ -330,7 +368,11 @@ class Recognizer:
     best keyword-gap-value placement (decode.ctc_keyed_field_reader on the same
     forward's logits, with keyed_gap_cost nats per frame of gap) scores at
     least keyed_threshold (default ln 0.5). One more entry call per batch (four
-    launches), none without keyed_fields. Not combined with lexicon."""
+    launches), none without keyed_fields. Not combined with lexicon.
+
+    Wherever a batch and its widths are taken as NumPy arrays, a uint8 device
+    tensor [bs, 32, W, 1] and an int32 device tensor [bs] are taken too and read
+    where they lie (page() feeds the crops of a whole page this way)."""
 
     def __init__(self, store, decoder="greedy", beam_width=16, merge_repeated=True, allow_bf16=False,
                  graphs=False, detail=False, lexicon=None, lexicon_top=1, keywords=None,
@@ -384,8 +426,11 @@ class Recognizer:
             g = self.graphs[key] = InferGraph(self.store, batch=shape[0], width=shape[2],
                                               decoder="greedy" if decoded and self.decoder == "greedy" else None,
                                               merge_repeated=self.merge_repeated)
-        return g.run(torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)),
-                     torch.from_numpy(np.asarray(widths, np.int32)))
+        if not isinstance(batch, torch.Tensor):
+            batch = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8))
+        if not isinstance(widths, torch.Tensor):
+            widths = torch.from_numpy(np.asarray(widths, np.int32))
+        return g.run(_checked_batch(batch), _checked_widths(widths))
 
     def labels(self, batch, widths):
         """Dense int64 [bs, max_len] (-1 padded) device tensor. graphs=True: the
@@ -400,8 +445,8 @@ class Recognizer:
             out, _ = decode.ctc_beam_search_decoder(g.logits, g.seq_len, self.beam_width, 1, self.merge_repeated)
             return out[0]
         with torch.no_grad():
-            image = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
-            width = torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+            image = _device_batch(batch, dev)
+            width = _device_widths(widths, dev)
             features, seq_len = convnet_layers(image, width, INFER, self.store)
             logits = rnn_layers(features, seq_len, num_classes(), self.store)
             if self.decoder == "greedy":
@@ -420,8 +465,8 @@ class Recognizer:
                 return logits, seq_len, g.decoded, g.decoded_len
         else:
             with torch.no_grad():
-                image = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
-                width = torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+                image = _device_batch(batch, dev)
+                width = _device_widths(widths, dev)
                 features, seq_len = convnet_layers(image, width, INFER, self.store)
                 logits = rnn_layers(features, seq_len, num_classes(), self.store)
             if self.decoder == "greedy":
@@ -453,7 +498,7 @@ class Recognizer:
         ln, status = ints[:, -2].tolist(), ints[:, -1].tolist()
         if any(status):
             K.clear_status(self.store.device, _lib.STATUS_CTC)
-        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], np.asarray(widths, np.float64)[:, None])
+        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], _host_widths(widths)[:, None])
         px = np.stack([x0, x1], axis=2).tolist()
         conf, loss, lab = flts[:, :n_max].tolist(), flts[:, -1].tolist(), lab.tolist()
         res = []
@@ -474,8 +519,8 @@ class Recognizer:
         else:
             dev = self.store.device
             with torch.no_grad():
-                image = torch.from_numpy(np.ascontiguousarray(batch, dtype=np.uint8)).to(dev, non_blocking=True)
-                width = torch.from_numpy(np.asarray(widths, np.int32)).to(dev, non_blocking=True)
+                image = _device_batch(batch, dev)
+                width = _device_widths(widths, dev)
                 features, seq_len = convnet_layers(image, width, INFER, self.store)
                 logits = rnn_layers(features, seq_len, num_classes(), self.store)
         with torch.no_grad():
@@ -509,7 +554,7 @@ class Recognizer:
         ln, status = ints[:, -2].tolist(), ints[:, -1].tolist()
         if any(status):                                     # a row without a word and without frames (seq_len 0)
             K.clear_status(self.store.device, _lib.STATUS_CTC)
-        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], np.asarray(widths, np.float64)[:, None])
+        x0, x1 = decode.frames_to_px(span[:, :, 0], span[:, :, 1], _host_widths(widths)[:, None])
         px = np.stack([x0, x1], axis=2).tolist()
         logp, log_norm, conf = flts[:, :k].tolist(), flts[:, k].tolist(), flts[:, k + 1:].tolist()
         words = self.lexicon.words
@@ -553,7 +598,7 @@ class Recognizer:
         order = np.lexsort((ks, -score[bs, ks], bs))
         bs, ks = bs[order], ks[order]
         first, end = span[bs, ks, 0], span[bs, ks, 1]
-        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        x0, x1 = decode.frames_to_px(first, end, _host_widths(widths)[bs])
         words = self.keywords.keywords
         hits = [[] for _ in texts]
         for b, k, s, f, e, a0, a1 in zip(bs.tolist(), ks.tolist(), score[bs, ks].tolist(), first.tolist(),
@@ -573,7 +618,7 @@ class Recognizer:
         order = np.lexsort((ks, errors[bs, ks], -score[bs, ks], bs))
         bs, ks = bs[order], ks[order]
         first, end = span[bs, ks, 0], span[bs, ks, 1]
-        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        x0, x1 = decode.frames_to_px(first, end, _host_widths(widths)[bs])
         words = self.keywords.keywords
         hits = [[] for _ in texts]
         for b, k, s, f, e, a0, a1, n in zip(bs.tolist(), ks.tolist(), score[bs, ks].tolist(), first.tolist(),
@@ -602,7 +647,7 @@ class Recognizer:
         order = np.lexsort((ps, -score[bs, ps], bs))
         bs, ps = bs[order], ps[order]
         first, end = span[bs, ps, 0], span[bs, ps, 1]
-        x0, x1 = decode.frames_to_px(first, end, np.asarray(widths, np.float64)[bs])
+        x0, x1 = decode.frames_to_px(first, end, _host_widths(widths)[bs])
         strings = self.fields.strings(text[bs, ps]) if len(bs) else []
         names = self.fields.names
         found = [[] for _ in base]
@@ -634,7 +679,7 @@ class Recognizer:
         order = np.lexsort((ps, -score[bs, ps], bs))
         bs, ps = bs[order], ps[order]
         sp = span[bs, ps]
-        w = np.asarray(widths, np.float64)[bs]
+        w = _host_widths(widths)[bs]
         k0, k1 = decode.frames_to_px(sp[:, 0], sp[:, 1], w)
         x0, x1 = decode.frames_to_px(sp[:, 2], sp[:, 3], w)
         strings = self.keyed_fields.strings(text[bs, ps]) if len(bs) else []
@@ -659,6 +704,23 @@ class Recognizer:
         if self.detail:
             return self.recognitions(batch, widths)
         return validate.decode_strings(self.labels(batch, widths))
+
+    def page(self, page, boxes, normalize=True, bucket_size=16, accept_narrow=False, pad=1):
+        """Read a page from its line boxes (pagepredictor.py:274, 319-328, then the bucketing of
+        LocalServer): page is uint8 or float32 [H, W] (NumPy, uploaded once, or a device tensor),
+        boxes integers [n, 4] of (y0, x0, y1, x1). page.plan_page buckets the boxes, page.page_crops
+        cuts, resizes and pads every crop on the device in one launch, and each batch is recognised
+        where it lies. Returns PageLines(results, skipped): results[i] is what __call__ returns for
+        the crop of box i, None for a box the plan skipped."""
+        from . import page as P
+        plan = P.plan_page(boxes, tuple(page.shape), bucket_size, accept_narrow, pad)
+        results = [None] * plan.n_boxes
+        crops = P.page_crops(page, plan, normalize, device=self.store.device)
+        for (batch, widths), planned in zip(crops, plan.batches):
+            for res, box in zip(self(batch, widths), planned.boxes.tolist()):
+                if box >= 0:                                 # a top-up row's result is dropped
+                    results[box] = res
+        return PageLines(results, plan.skipped)
 
 
 class LocalServer:

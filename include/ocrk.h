@@ -40,7 +40,7 @@ enum ocrk_status {
     OCRK_ERR_INFEASIBLE = 3 /* CTC: label longer than the input sequence allows */
 };
 
-enum ocrk_dtype { OCRK_F32 = 0, OCRK_BF16 = 1 };
+enum ocrk_dtype { OCRK_F32 = 0, OCRK_BF16 = 1, OCRK_U8 = 2 /* page images only (ocrk_page_*) */ };
 
 /* How OCRK_F32 operands are multiplied by every GEMM / implicit-GEMM conv entry point
  * (process-wide -- torch's autograd issues a backward's launches from its own device
@@ -806,6 +806,32 @@ int ocrk_mul_scalar(float* x, int64_t n, const float* s, void* stream);
 int ocrk_mean(const float* x, int n, float* out, void* stream);
 /* model.py:152-163: seq_len = floor((width - 2) / 2) - 2 */
 int ocrk_seq_len(const int* widths, int n, int* out, void* stream);
+
+/* ------------------------------------------------- page -> line crops
+ * What src/processing/pagepredictor.py:274, 319-328 does on the host per line box
+ * (cv2.normalize NORM_MINMAX of the page, the box cut, cv2.resize to height 32, * 255 as
+ * uint8) together with server.py:29-34's zero padding to the bucket width and
+ * server.py:123-128's zero top-up crops, for every box of a page in one launch.
+ *
+ * ocrk_page_minmax: minmax[0] = min, minmax[1] = max of the n pixels of `page` (dtype
+ * OCRK_U8 or OCRK_F32; NaNs are passed over). ws: 16 bytes of device memory, zeroed by the
+ * entry (a stream-ordered memset). Deterministic: min and max do not depend on the order.
+ *
+ * ocrk_page_crops: page [H][W] (OCRK_U8 or OCRK_F32, dense). jobs: i32 [njobs][8] in device
+ * memory (16-byte aligned) and the same table in host memory (jobs_host), one row per
+ * output crop: {y0, x0, h, w, nw, Wb, offset / 32, box}. The crop is the 32 x nw bilinear
+ * resize (half-pixel centres, the rule of cv2.resize INTER_LINEAR, positions from integers)
+ * of page[y0 : y0 + h, x0 : x0 + w], written as uint8 rows of Wb bytes at arena + 32 *
+ * (offset / 32), columns nw..Wb-1 zero; box < 0 with nw == 0 is a top-up crop, all zero.
+ * A pixel is clamp(floor((value - lo) * gain), 0, 255): with minmax (device, as written by
+ * ocrk_page_minmax) lo = min and gain = scale / (max - min), 0 when max == min; with
+ * minmax == NULL lo = 0 and gain = scale. The host table is validated before the launch:
+ * every source rectangle inside the page, every written span inside the arena's
+ * arena_bytes, 1 <= nw <= Wb, Wb a multiple of 32; on a violation OCRK_ERR_INVALID_ARG and
+ * nothing is launched. Nothing outside the jobs' spans is written. */
+int ocrk_page_minmax(const void* page, int dtype, int64_t n, float* minmax, void* ws, void* stream);
+int ocrk_page_crops(const void* page, int dtype, int H, int W, const int* jobs, const int* jobs_host, int njobs,
+                    uint8_t* arena, int64_t arena_bytes, const float* minmax, float scale, void* stream);
 
 /* Launch-probe timers (bench.py's roofline leg; no reference counterpart).
  * A hipEvent_t behind an opaque handle; ocrk_timer_record on a stream that is
